@@ -17,6 +17,13 @@ communication.
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
   python bench.py --gpus N ...   (no launcher: starts the N ranks itself, launch_ranks)
 
+A plain run sets up, warms up, times the K steps and prints the result line
+(the roofline figures in it come from the timed steps' own stage times and the
+committed PMC summaries; they take no run of their own).  --full adds the legs
+that do: the determinism soak, the held-out corpus leg and the CPU baselines
+(--soak-s, --no-heldout and --no-cpu-baseline trim them).  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy.
+
 --task selects the other BASELINE configs (not the headline line):
   span         configs[2]: t5 Unigram, seq_len=512, batch=256, T5Data span
                corruption with the reference's Span{16.0, 2.0}
@@ -350,8 +357,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the determinism soak (--soak-s), the "
+                         "held-out corpus leg and the CPU baselines (off by default: a plain run times the steps "
+                         "and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the planes a caller receives; "
+                         "a fixed seeded sample of rows when they exceed the size cap) as DIR/<name>.npy")
     ap.add_argument("--soak-s", type=float, default=4.0,
-                    help="after the timed region (never part of it): re-run the step for this long and check "
+                    help="with --full, after the timed region (never part of it): re-run the step for this long and check "
                          "that every run writes the same planes as the timed one (device checksums); 0: off")
     ap.add_argument("--task", default="mlm", choices=sorted(TASKS))
     ap.add_argument("--arena-mib", type=int, default=256)
@@ -361,7 +375,7 @@ def parse_args(argv=None):
                          "a second kernel-tuning corpus, not an untouched one)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-heldout", action="store_true",
-                    help="skip the held-out corpus leg (by default a fixture run also times the same config on "
+                    help="skip the held-out corpus leg (with --full a fixture run also times the same config on "
                          "the held-out corpus and reports it under `heldout`, beside `value`)")
     ap.add_argument("--rng-mode", type=int, default=0, choices=[0, 1],
                     help="0 the Philox contract (default); 1 the reference's own draws on a per-row StdRng: "
@@ -496,6 +510,37 @@ def determinism_soak(step, res, rows, task, dev, seconds):
             sys.exit(4)
     log(f"determinism soak: {n} more runs in {time.perf_counter() - t0:.1f} s, identical planes")
     return {"runs": n, "seconds": round(time.perf_counter() - t0, 2), "identical": True}
+
+
+DUMP_CAP_BYTES = 48 << 20  # all files of one --dump-outputs together (float32 planes + the two small arrays)
+
+
+def dump_outputs(out_dir, res, rows, toks):
+    """--dump-outputs: the planes a caller of the timed path receives from its
+    last step (DeviceResult.tensors: input_ids, attention_mask, token_type_ids
+    when the task has them, labels) as <name>.npy, float32 (ids, masks and
+    labels are integers below 2^24 or small floats: exact).  When the planes
+    exceed DUMP_CAP_BYTES the same seeded sample of rows is taken from every
+    plane; `sample_rows.npy` lists it, `counts.npy` holds [rows, tokens] and
+    `<name>_sums.npy` each whole plane's (sum, sum of odd elements) in float64,
+    so the rows left out still show in the comparison."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    planes = res.tensors(rows) if rows else {}
+    row_bytes = 4 * sum(int(t.shape[1]) for t in planes.values())
+    keep = min(rows, DUMP_CAP_BYTES // row_bytes) if row_bytes else 0
+    idx = np.arange(rows, dtype=np.int64) if keep == rows else \
+        np.sort(np.random.default_rng(0xD0A7).choice(rows, size=keep, replace=False)).astype(np.int64)
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([rows, toks], np.float64))
+    np.save(os.path.join(out_dir, "sample_rows.npy"), idx.astype(np.float64))
+    for name, t in planes.items():
+        flat = t.reshape(-1)
+        acc = torch.float64 if t.dtype.is_floating_point else torch.int64
+        sums = [float(flat.sum(dtype=acc)), float(flat[1::2].sum(dtype=acc))]
+        np.save(os.path.join(out_dir, f"{name}_sums.npy"), np.array(sums, np.float64))
+        part = t.index_select(0, torch.from_numpy(idx).to(t.device)).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), part)
+    log(f"dumped {keep} of {rows} rows of {sorted(planes)} to {out_dir}")
 
 
 def _build_id():
@@ -714,7 +759,9 @@ def main(argv=None):
         sys.exit(3)
 
     rows, toks = res.rows(), res.tokens()
-    soak = determinism_soak(step, res, rows, task, dev, args.soak_s) if args.soak_s > 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, rows, toks)
+    soak = determinism_soak(step, res, rows, task, dev, args.soak_s) if args.full and args.soak_s > 0 else None
     stage_ms = {k: v / args.steps for k, v in stage_sum.items()}
     tok_ms = stage_ms["tokenize"]
     step_ms = dt / args.steps * 1e3
@@ -770,13 +817,13 @@ def main(argv=None):
                                              json_mib=args.arena_mib, N_text=N)
     if args.frames and rank == 0:
         line["transport_frames"] = transport_frames(db, res, args.task, stream, dev, args.steps, args.warmup,
-                                                    not args.no_cpu_baseline)
+                                                    args.full and not args.no_cpu_baseline)
     if args.e2e_frames and rank == 0 and args.task in ("mlm", "clm", "span"):
         # last: it reuses the handle's workspace (the step's planes are overwritten)
         line["end_to_end_frames"] = end_to_end_frames(db, records, order, dev, stream, args.task)
-    if args.corpus == "fixture" and not args.no_heldout:  # (after the legs that reuse the step's result)
+    if args.full and args.corpus == "fixture" and not args.no_heldout:  # (after the legs that reuse the step's result)
         line["heldout"] = heldout_leg(args, db, dev, stream, task, world, rank, barrier)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline ...")
         line["cpu_baseline"] = cpu_baseline(args.task, records, order)
         line["cpu_baseline"]["reference_engine"] = reference_engine_rate(args.task, records, order)

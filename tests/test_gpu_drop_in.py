@@ -140,7 +140,7 @@ def test_drained_simple_batcher_multi_label(native_lib):
 def test_bench_spawn_path_reports_one_gpu(native_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "1", "--spawn", "--steps", "2",
-                        "--warmup", "1", "--arena-mib", "8", "--no-cpu-baseline"],
+                        "--warmup", "1", "--arena-mib", "8", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=110, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -148,3 +148,30 @@ def test_bench_spawn_path_reports_one_gpu(native_lib):
     # the held-out leg rides along with a fixture run, beside `value`
     h = d["heldout"]
     assert h["value"] > 0 and h["errors"] == {"tokenize": 0, "label": 0} and h["roofline"]["avg_launch_ms"] > 0
+    assert d["determinism"]["identical"]
+
+
+def test_bench_plain_run_dumps_its_outputs(native_lib, tmp_path):
+    """A plain run carries none of the --full legs; --dump-outputs writes the last timed step's
+    planes as float32 <name>.npy (every row at this size), consistent with the whole-plane sums
+    and the row / token counts written beside them."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1", "--arena-mib", "8", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=110, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert "heldout" not in d and "determinism" not in d and d["cpu_baseline"] is None
+    rows, toks = np.load(tmp_path / "counts.npy")
+    assert (rows, toks) == (d["config"]["rows_per_gpu"], d["config"]["ids_per_gpu"])
+    np.testing.assert_array_equal(np.load(tmp_path / "sample_rows.npy"), np.arange(rows))
+    total = 0
+    for name in ("input_ids", "attention_mask", "token_type_ids", "labels"):
+        a = np.load(tmp_path / f"{name}.npy")
+        total += a.nbytes
+        assert a.dtype == np.float32 and a.shape == (rows, 512)
+        s = np.load(tmp_path / f"{name}_sums.npy")
+        assert s.dtype == np.float64
+        assert (a.sum(dtype=np.float64), a.reshape(-1)[1::2].sum(dtype=np.float64)) == tuple(s)
+    assert total <= 64 << 20
