@@ -15,10 +15,11 @@ hipError_t launch_chunk_ranges(const uint64_t *off, int64_t R, int64_t N, uint32
                                uint32_t *rb1 = nullptr, uint32_t *zero1 = nullptr, const void *copy_src = nullptr,
                                void *copy_dst = nullptr, size_t copy_bytes = 0);
 
-// tokenize_wordpiece.hip: text arena -> per-chunk token lists + boundary offsets
-// (after launch_chunk_ranges), for chunks [c_begin, c_end) (c_end < 0: all).
+// tokenize_wordpiece.hip: text arena -> per-chunk token lists (packed u16, STAGE
+// slots a chunk) + boundary offsets (after launch_chunk_ranges), for chunks
+// [c_begin, c_end) (c_end < 0: all).
 hipError_t launch_wordpiece_chunks(const DevTok &T, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
-                                   uint32_t *ranges, uint32_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
+                                   uint32_t *ranges, uint16_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
                                    hipStream_t st, int64_t c_begin = 0, int64_t c_end = -1);
 
 // tokenize_bpe.hip: same outputs for a byte-level BPE (gpt2) tokenizer.  Pieces
@@ -207,10 +208,12 @@ hipError_t launch_scan_range(const uint32_t *in, uint32_t *out, const uint32_t *
 // long_count == null: no long-piece markers (WordPiece).  Else chunk_ent holds
 // each chunk's entry count (markers count 1; chunk_cnt counts ids).
 // long_pool != null (unigram): a marker's ids are long_pool[off + 1 ..], count long_pool[off].
+// list16: tokc holds packed u16 lists, stride u16 slots a chunk (WordPiece: no markers).
 hipError_t launch_compact_tokens(const uint32_t *tokc, const uint32_t *chunk_cnt, const uint32_t *chunk_off,
                                  int64_t n_chunks, uint32_t *tok, const uint32_t *long_count,
                                  const uint32_t *chunk_ent, const BpeLong *long_list, const uint16_t *long_scratch,
-                                 hipStream_t st, const uint32_t *long_pool = nullptr, int64_t stride = STAGE);
+                                 hipStream_t st, const uint32_t *long_pool = nullptr, int64_t stride = STAGE,
+                                 bool list16 = false);
 
 
 // Which records / rows a launch covers: records [rb[k], rb[k+1]), rows
@@ -254,6 +257,7 @@ struct SmallDown {
     const uint16_t *long_scratch;
     const uint32_t *long_pool;
     int64_t stride;
+    int list16;  // tokc holds packed u16 lists, stride u16 slots a chunk (WordPiece)
     const uint32_t *rec_local;
     uint32_t *rec_tok, *rec_cnt, *rec_rows, *row_off, *row_rec;
     uint32_t *stat;  // or null: row_off[0..R], a zero label-error word and the tokenizer's error word
@@ -265,8 +269,28 @@ struct SmallDown {
 hipError_t launch_downstream_small(const SmallDown &d, const RowParams &P, const uint64_t *off, int64_t R, int64_t N,
                                    hipStream_t st);
 
-// row -> record map (row_rec needs one word per row)
-hipError_t launch_row_map(const uint32_t *row_off, int64_t R, uint32_t *row_rec, SegSel sel, hipStream_t st);
+// Where the rows kernels read a call's ids: the dense array `tok`, or -- lists != null -- the
+// WordPiece chunk lists as the tokenizer wrote them (packed u16, STAGE slots a chunk;
+// list_index.hpp), which spares the copy into `tok`.
+struct TokSrc {
+    const uint32_t *tok;
+    const uint16_t *lists;
+    const uint32_t *chunk_off;  // [0 .. n_lists], chunk_off[n_lists] = the ids of chunks < n_lists
+    int64_t n_lists;            // chunks scanned so far (pipelined segments: the segment's end)
+    const uint32_t *row_chunk;  // row -> the chunk of its first id (k_row_map)
+};
+
+// row -> record map (row_rec needs one word per row).  rc (optional): also row -> the chunk of its
+// first id (TokSrc.row_chunk), found as each record's rows are walked.
+struct RowChunkIn {
+    uint32_t *row_chunk;
+    const uint32_t *rec_tok, *rec_cnt, *chunk_off;
+    const uint64_t *off;
+    int64_t n_lists;
+    int32_t S, n_pre, chunk;
+};
+hipError_t launch_row_map(const uint32_t *row_off, int64_t R, uint32_t *row_rec, SegSel sel, hipStream_t st,
+                          const RowChunkIn *rc = nullptr);
 
 // BertData::put_data + mask_batch for every row (models/bert_data.rs:40-89)
 // pipeline.hip: device rows -> finished batches in pinned host memory (the
@@ -285,7 +309,7 @@ hipError_t launch_rows_direct(const DirectDst &d, const uint32_t *row_off, int64
                               const int32_t *am, const int32_t *tt, const int32_t *lab, int S, int LW,
                               const uint32_t *err0, const uint32_t *err1, uint32_t *stat, hipStream_t st);
 
-hipError_t launch_rows(const RowParams &P, const uint32_t *tok, const uint32_t *rec_tok, const uint32_t *rec_cnt,
+hipError_t launch_rows(const RowParams &P, const TokSrc &src, const uint32_t *rec_tok, const uint32_t *rec_cnt,
                        const uint32_t *row_off, const uint32_t *row_rec, SegSel sel, int64_t rows_cap, RowOut out,
                        hipStream_t st,
                        hipStream_t st_late = nullptr);

@@ -252,7 +252,7 @@ hipError_t launch_chunk_ranges(const uint64_t *off, int64_t R, int64_t N, uint32
 // ---------------------------------------------------------------------------
 // Per-chunk token lists -> one dense token array in arena order.
 // ---------------------------------------------------------------------------
-template <int PART>
+template <int PART, bool E16 = false>
 __global__ __launch_bounds__(256) void k_compact_tokens(const uint32_t *__restrict__ tokc,
                                                         const uint32_t *__restrict__ chunk_cnt,
                                                         const uint32_t *__restrict__ chunk_off, int64_t n_chunks,
@@ -263,16 +263,21 @@ __global__ __launch_bounds__(256) void k_compact_tokens(const uint32_t *__restri
                                                         const uint32_t *__restrict__ long_pool, int64_t stride) {
     const int64_t cb = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * COMPACT_CPW;  // the wave's first chunk
     if (cb >= n_chunks) return;
-    compact_wave<PART>(cb, tokc, chunk_cnt, chunk_off, n_chunks, tok, long_count, chunk_ent, long_list, long_scratch,
-                       long_pool, stride);
+    compact_wave<PART, E16>(cb, tokc, chunk_cnt, chunk_off, n_chunks, tok, long_count, chunk_ent, long_list,
+                            long_scratch, long_pool, stride);
 }
 
 hipError_t launch_compact_tokens(const uint32_t *tokc, const uint32_t *chunk_cnt, const uint32_t *chunk_off,
                                  int64_t n_chunks, uint32_t *tok, const uint32_t *long_count,
                                  const uint32_t *chunk_ent, const BpeLong *long_list, const uint16_t *long_scratch,
-                                 hipStream_t st, const uint32_t *long_pool, int64_t stride) {
+                                 hipStream_t st, const uint32_t *long_pool, int64_t stride, bool list16) {
     if (n_chunks == 0) return hipSuccess;
     const int64_t waves = (n_chunks + COMPACT_CPW - 1) / COMPACT_CPW;
+    if (list16) {  // (WordPiece's u16 lists, for the rows kernels that read the dense array: span)
+        hipLaunchKernelGGL((k_compact_tokens<1, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, tokc,
+                           chunk_cnt, chunk_off, n_chunks, tok, nullptr, nullptr, nullptr, nullptr, nullptr, stride);
+        return hipGetLastError();
+    }
     // (byte-level BPE / unigram: the long-item copy as its own kernel; one of the two has work)
     hipLaunchKernelGGL(k_compact_tokens<1>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, tokc, chunk_cnt,
                        chunk_off, n_chunks, tok, long_count, chunk_ent, long_list, long_scratch, long_pool, stride);
@@ -302,12 +307,30 @@ hipError_t launch_records(const RowParams &P, const uint64_t *off, int64_t R, in
     return hipGetLastError();
 }
 
-// Row g -> its record (one thread per record writes its rows' entries).
+// Row g -> its record (one thread per record writes its rows' entries).  RC: and the chunk whose
+// list holds the row's first id (TokSrc.row_chunk) -- the rows of a record start at rising id
+// indices, so each search starts at the previous row's chunk.
+template <bool RC>
 __global__ __launch_bounds__(256) void k_row_map(const uint32_t *__restrict__ row_off, uint32_t *__restrict__ row_rec,
-                                                 SegSel sel) {
+                                                 SegSel sel, RowChunkIn rc) {
     const int64_t r_lo = sel.rb[sel.k], r_hi = sel.rb[sel.k + 1];
-    for (int64_t r = r_lo + (int64_t)blockIdx.x * 256 + threadIdx.x; r < r_hi; r += (int64_t)gridDim.x * 256)
-        for (uint32_t g = row_off[r]; g < row_off[r + 1]; ++g) row_rec[g] = (uint32_t)r;
+    for (int64_t r = r_lo + (int64_t)blockIdx.x * 256 + threadIdx.x; r < r_hi; r += (int64_t)gridDim.x * 256) {
+        const uint32_t g0 = row_off[r], g1 = row_off[r + 1];
+        if constexpr (RC) {
+            if (g0 == g1) continue;
+            ListBracket br = list_bracket(rc.off[r], rc.off[r + 1], rc.n_lists);
+            const uint32_t t0 = rc.rec_tok[r], cnt = rc.rec_cnt[r];
+            for (uint32_t g = g0; g < g1; ++g) {
+                row_rec[g] = (uint32_t)r;
+                const int64_t base = rc.chunk ? (int64_t)(g - g0) * rc.S : 0;
+                const int64_t rel0 = base > rc.n_pre ? base - rc.n_pre : 0;  // the row's first id of the record's
+                if (rel0 < (int64_t)cnt) br.lo = list_chunk_of(rc.chunk_off, br.lo, br.hi, t0 + (uint32_t)rel0);
+                rc.row_chunk[g] = (uint32_t)br.lo;
+            }
+        } else {
+            for (uint32_t g = g0; g < g1; ++g) row_rec[g] = (uint32_t)r;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -335,10 +358,13 @@ __device__ __forceinline__ void block_scan_small(const uint32_t *__restrict__ in
     if (threadIdx.x == 0) out[n] = tot;
 }
 
-hipError_t launch_row_map(const uint32_t *row_off, int64_t R, uint32_t *row_rec, SegSel sel, hipStream_t st) {
+hipError_t launch_row_map(const uint32_t *row_off, int64_t R, uint32_t *row_rec, SegSel sel, hipStream_t st,
+                          const RowChunkIn *rc) {
     if (R == 0) return hipSuccess;
     const int64_t want = (R + 255) / 256;
-    hipLaunchKernelGGL(k_row_map, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, row_off, row_rec, sel);
+    const dim3 grid((unsigned)(want < 1024 ? want : 1024));
+    if (rc) hipLaunchKernelGGL(k_row_map<true>, grid, dim3(256), 0, st, row_off, row_rec, sel, *rc);
+    else hipLaunchKernelGGL(k_row_map<false>, grid, dim3(256), 0, st, row_off, row_rec, sel, RowChunkIn{});
     return hipGetLastError();
 }
 
@@ -479,13 +505,15 @@ __device__ __forceinline__ void rand_rows16(const RowParams &P, int nrows, uint6
 // per SIMD (k_rows<2>: 80 -> 82 VGPRs, 6 -> 5 waves, 0.267 -> 0.295 ms).
 // LATE (RM1 only): the second pass over the rows the first one left (no mask bits from beside the
 // tokenizer): its waves walk their masks in place, 4 rows at a time (rand_rows16).
-template <int MR, bool RM1, bool LATE = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MR >= 4 ? ROWS_WAVES4 : LATE ? 4 : RM1 ? ROWS_WAVES_RM1 : ROWS_WAVES, 8))) void k_rows(RowParams P, const uint32_t *__restrict__ tok,
+// LISTS: the ids come from the WordPiece chunk lists (TokSrc; row_one), not from a dense array.
+template <int MR, bool RM1, bool LATE = false, bool LISTS = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MR >= 4 ? ROWS_WAVES4 : LATE ? 4 : RM1 ? ROWS_WAVES_RM1 : ROWS_WAVES, 8))) void k_rows(RowParams P, TokSrc tok,
                                               const uint32_t *__restrict__ rec_tok, const uint32_t *__restrict__ rec_cnt,
                                               const uint32_t *__restrict__ row_off, const uint32_t *__restrict__ row_rec,
                                               SegSel sel, int64_t rows_cap, RowOut out) {
     const int lane = lane_id();
-    const int wid = (int)(threadIdx.x >> 6);
+    // (LISTS: told to the compiler as wave-uniform, so the row's scalars live in SGPRs)
+    const int wid = LISTS ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
     // (LATE: a wave's LDS for rand_rows16 -- 4 windows, 4 next() arrays + dummy slots, 4 rows' bits)
     constexpr int NXS = 256 * MR + 1, BW = 8 * MR;
     __shared__ __attribute__((aligned(16))) uint32_t s_rw[LATE ? 4 : 1][LATE ? 4 * (NXS + BW) : 1];
@@ -518,14 +546,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MR >= 4 ? R
                 }
                 rand_rows16(P, nr, rec, kq, rw, bits, BW, lane);
                 for (int q = 0; q < nr; ++q, m &= m - 1)
-                    row_one<MR, RM1, LATE>(P, tok, rec_tok, rec_cnt, row_off, row_rec, g0 + __builtin_ctzll(m), G, out,
+                    row_one<MR, RM1, LATE, LISTS>(P, tok, rec_tok, rec_cnt, row_off, row_rec, g0 + __builtin_ctzll(m), G, out,
                                            bits + BW * q, lane);
                 __builtin_amdgcn_wave_barrier();  // (the LDS is rewritten by the next rows)
             }
         }
     } else {
         for (int64_t g = rs.g_lo + (int64_t)blockIdx.x * 4 + wid; g < g_end; g += (int64_t)gridDim.x * 4)
-            row_one<MR, RM1, LATE>(P, tok, rec_tok, rec_cnt, row_off, row_rec, g, G, out, nullptr, lane);
+            row_one<MR, RM1, LATE, LISTS>(P, tok, rec_tok, rec_cnt, row_off, row_rec, g, G, out, nullptr, lane);
     }
 }
 
@@ -538,8 +566,7 @@ __global__ __launch_bounds__(SCAN_SMALL_NT) void k_downstream_small(SmallDown d,
     __syncthreads();
     for (int64_t cb = (int64_t)(threadIdx.x >> 6) * COMPACT_CPW; cb < n_chunks;
          cb += (int64_t)(SCAN_SMALL_NT / 64) * COMPACT_CPW)
-        compact_wave(cb, d.tokc, d.chunk_cnt, d.chunk_off, n_chunks, d.tok, d.long_count, d.chunk_ent, d.long_list,
-                     d.long_scratch, d.long_pool, d.stride);
+        compact_small(d, cb, d.chunk_off, n_chunks);
     for (int64_t r = threadIdx.x; r < R; r += SCAN_SMALL_NT)
         record_one(P, off, r, N, d.chunk_off, n_chunks, d.rec_local, d.rec_tok, d.rec_cnt, d.rec_rows);
     __syncthreads();
@@ -559,7 +586,7 @@ __global__ __launch_bounds__(SCAN_SMALL_NT) void k_downstream_small(SmallDown d,
         const int64_t G = (int64_t)d.row_off[R];
         const int64_t g_end = d.out.direct.cap ? G : (G + P.B - 1) / P.B * P.B;
         for (int64_t g = (int64_t)(threadIdx.x >> 6); g < g_end; g += SCAN_SMALL_NT / 64)
-            row_one<MR, false, false>(P, d.tok, d.rec_tok, d.rec_cnt, d.row_off, d.row_rec, g, G, d.out, nullptr,
+            row_one<MR, false, false>(P, TokSrc{d.tok}, d.rec_tok, d.rec_cnt, d.row_off, d.row_rec, g, G, d.out, nullptr,
                                       lane_id());
     }
 }
@@ -934,7 +961,7 @@ hipError_t launch_rows_direct(const DirectDst &d, const uint32_t *row_off, int64
     return hipGetLastError();
 }
 
-hipError_t launch_rows(const RowParams &P, const uint32_t *tok, const uint32_t *rec_tok, const uint32_t *rec_cnt,
+hipError_t launch_rows(const RowParams &P, const TokSrc &tok, const uint32_t *rec_tok, const uint32_t *rec_cnt,
                        const uint32_t *row_off, const uint32_t *row_rec, SegSel sel, int64_t rows_cap, RowOut out,
                        hipStream_t st, hipStream_t st_late) {
     if (!st_late) st_late = st;
@@ -950,21 +977,30 @@ constexpr int ROWS_GRID_CAP = 16384;
     // (rng_mode 1: the late pass scans 256 rows a block)
     const int64_t want_late = (rows_cap + 255) / 256;
     const unsigned grid_late = (unsigned)(want_late < 2048 ? want_late : 2048);
-#define LAUNCH_ROWS(MM)                                                                                                 \
+#define LAUNCH_ROWS_L(MM, LL)                                                                                           \
     if (rm1) {                                                                                                        \
-        hipLaunchKernelGGL((k_rows<MM, true>), dim3(grid), dim3(256), 0, st, P, tok, rec_tok, rec_cnt, row_off,      \
-                           row_rec, sel, rows_cap, out);                                                              \
-        hipLaunchKernelGGL((k_rows<MM, true, true>), dim3(grid_late), dim3(256), 0, st_late, P, tok, rec_tok, rec_cnt, \
+        hipLaunchKernelGGL((k_rows<MM, true, false, LL>), dim3(grid), dim3(256), 0, st, P, tok, rec_tok, rec_cnt,    \
                            row_off, row_rec, sel, rows_cap, out);                                                     \
+        hipLaunchKernelGGL((k_rows<MM, true, true, LL>), dim3(grid_late), dim3(256), 0, st_late, P, tok, rec_tok,    \
+                           rec_cnt, row_off, row_rec, sel, rows_cap, out);                                            \
     } else                                                                                                            \
-        hipLaunchKernelGGL((k_rows<MM, false>), dim3(grid), dim3(256), 0, st, P, tok, rec_tok, rec_cnt, row_off,     \
-                           row_rec, sel, rows_cap, out)
+        hipLaunchKernelGGL((k_rows<MM, false, false, LL>), dim3(grid), dim3(256), 0, st, P, tok, rec_tok, rec_cnt,   \
+                           row_off, row_rec, sel, rows_cap, out)
+#define LAUNCH_ROWS(MM)                                                                                                 \
+    do {                                                                                                              \
+        if (tok.lists) {                                                                                              \
+            LAUNCH_ROWS_L(MM, true);                                                                                  \
+        } else {                                                                                                      \
+            LAUNCH_ROWS_L(MM, false);                                                                                 \
+        }                                                                                                             \
+    } while (0)
     if (MR <= 1) LAUNCH_ROWS(1);
     else if (MR <= 2) LAUNCH_ROWS(2);
     else if (MR <= 4) LAUNCH_ROWS(4);
     else if (MR <= 8) LAUNCH_ROWS(8);
     else return hipErrorInvalidValue;
 #undef LAUNCH_ROWS
+#undef LAUNCH_ROWS_L
     return hipGetLastError();
 }
 

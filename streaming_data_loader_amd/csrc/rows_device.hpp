@@ -1,17 +1,23 @@
 // Device code shared by the rows kernels (pipeline.hip) and the fused tiny-push tail of the
 // WordPiece chunk kernel (tokenize_wordpiece.hip): chunk-list compaction, per-record framing,
-// the Philox mask contract and one row's planes.
+// the Philox mask contract and one row's planes.  A row's ids come from the dense array the
+// compaction makes, or (WordPiece, large calls: row_one<.., LISTS>) straight from the packed u16
+// chunk lists the tokenizer wrote, indexed as list_index.hpp says.
 #pragma once
 #include "common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
+#include "list_index.hpp"
 
 namespace sdl {
+
+static_assert(LIST_CHUNK == CHUNK && LIST_STRIDE == STAGE, "list_index.hpp restates the chunk geometry");
 
 constexpr int COMPACT_CPW = 4;  // chunks per wave: their loads are in flight together
 // one wave: chunks [cb, cb + COMPACT_CPW).  PART 1: only when the call has no long items, 2: only
 // when it has (separate kernels keep the plain copy's registers), 0: either.
-template <int PART = 0>
+// E16: the lists are packed u16 (WordPiece: stride u16 slots a chunk, no long items).
+template <int PART = 0, bool E16 = false>
 __device__ __forceinline__ void compact_wave(int64_t cb, const uint32_t *__restrict__ tokc,
                                              const uint32_t *__restrict__ chunk_cnt,
                                              const uint32_t *__restrict__ chunk_off, int64_t n_chunks,
@@ -29,8 +35,15 @@ __device__ __forceinline__ void compact_wave(int64_t cb, const uint32_t *__restr
         o[j] = in ? chunk_off[cb + j] : 0u;
     }
     // (unigram: Viterbi job markers are in every call's lists)
-    const bool has_long = long_count && (long_pool != nullptr || *long_count != 0);
+    const bool has_long = !E16 && long_count && (long_pool != nullptr || *long_count != 0);
     if ((PART == 1 && has_long) || (PART == 2 && !has_long)) return;
+    // entry i of chunk c's list
+    auto entry = [&](int64_t c, uint32_t i) -> uint32_t {
+        if constexpr (E16)
+            return __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(tokc) + c * stride + i);
+        else
+            return __builtin_nontemporal_load(tokc + c * stride + i);
+    };
     if (!has_long) {
         // lane-contiguous dwords: every store instruction writes 256 B of the
         // dense array back to back (at any alignment); the first 256 ids of all
@@ -41,7 +54,7 @@ __device__ __forceinline__ void compact_wave(int64_t cb, const uint32_t *__restr
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t i = 64 * k + lane;
-                v[j][k] = i < n[j] ? __builtin_nontemporal_load(tokc + (cb + j) * stride + i) : 0u;
+                v[j][k] = i < n[j] ? entry(cb + j, i) : 0u;
             }
 #pragma unroll
         for (int j = 0; j < COMPACT_CPW; ++j)
@@ -51,13 +64,12 @@ __device__ __forceinline__ void compact_wave(int64_t cb, const uint32_t *__restr
                 if (i < n[j]) tok[(uint64_t)o[j] + i] = v[j][k];
             }
         for (int j = 0; j < COMPACT_CPW; ++j) {  // chunks with more than 256 ids
-            const uint32_t *src = tokc + (cb + j) * stride;
             for (uint32_t i0 = 256; i0 < n[j]; i0 += 256) {
                 uint32_t w[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const uint32_t i = i0 + 64 * k + lane;
-                    w[k] = i < n[j] ? __builtin_nontemporal_load(src + i) : 0u;
+                    w[k] = i < n[j] ? entry(cb + j, i) : 0u;
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -68,6 +80,7 @@ __device__ __forceinline__ void compact_wave(int64_t cb, const uint32_t *__restr
         }
         return;
     }
+    if constexpr (E16) return;
     // byte-level BPE / unigram with long items: an entry LONG_MARK | i stands
     // for the k ids of long piece i (in long_scratch at its byte position) or
     // of pool item i; a unigram Viterbi job's entry LONG_MARK | UNI_JOB_BIT |
@@ -124,6 +137,17 @@ __device__ __forceinline__ void compact_wave(int64_t cb, const uint32_t *__restr
             written[j] += (uint32_t)lane_bcast((int)incl, 63);
         }
     }
+}
+
+// a small call's chunks [cb, cb + COMPACT_CPW) into its dense array: u16 lists (WordPiece) or u32 entries
+__device__ __forceinline__ void compact_small(const SmallDown &d, int64_t cb, const uint32_t *__restrict__ chunk_off,
+                                              int64_t n_chunks) {
+    if (d.list16)
+        compact_wave<0, true>(cb, d.tokc, d.chunk_cnt, chunk_off, n_chunks, d.tok, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, d.stride);
+    else
+        compact_wave(cb, d.tokc, d.chunk_cnt, chunk_off, n_chunks, d.tok, d.long_count, d.chunk_ent, d.long_list,
+                     d.long_scratch, d.long_pool, d.stride);
 }
 
 // ---------------------------------------------------------------------------
@@ -299,8 +323,16 @@ __device__ __forceinline__ void store4(int32_t *p, int j0, int S, bool vec, int3
 
 // One row g of the call (a wave): BertData::put_data (+ mask_batch) / GptData::put_data framing and
 // planes; g >= G: a padding row of the last batch.  late_bits: the row's mask words (LATE).
-template <int MR, bool RM1, bool LATE>
-__device__ __forceinline__ void row_one(const RowParams &P, const uint32_t *__restrict__ tok,
+//
+// LISTS: the ids are read from the WordPiece chunk lists themselves (TokSrc, list_index.hpp), not
+// from a dense copy.  The row's first id lies in chunk c = row_chunk[g] (k_row_map).  One
+// coalesced load gives lane b the boundary chunk_off[c + b]; a row normally ends 3-4 chunks on, so
+// every id's chunk is a count of the few boundaries at or below its index (wave-uniform walk over
+// them) and its list's start a cross-lane read of the loaded boundaries: no dependent global load
+// between the boundaries and the ids.  A row that runs past the 63 loaded boundaries (a long run
+// of chunks without ids) searches chunk_off per lane instead -- any span.
+template <int MR, bool RM1, bool LATE, bool LISTS = false>
+__device__ __forceinline__ void row_one(const RowParams &P, const TokSrc &src,
                                         const uint32_t *__restrict__ rec_tok, const uint32_t *__restrict__ rec_cnt,
                                         const uint32_t *__restrict__ row_off, const uint32_t *__restrict__ row_rec,
                                         int64_t g, int64_t G, const RowOut &out, const uint32_t *late_bits,
@@ -331,6 +363,14 @@ __device__ __forceinline__ void row_one(const RowParams &P, const uint32_t *__re
         }
         return;
     }
+    // (LISTS) the row's first chunk c and the boundaries from it on, lane b's chunk_off[c + b]:
+    // loaded here, beside the record's fields, not after them (every row has a valid c)
+    const int64_t nl = LISTS ? src.n_lists : 0;
+    uint32_t c = 0, bnd = 0;  // bnd(0) <= the row's first id < bnd(1)
+    if constexpr (LISTS) {
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)src.row_chunk[g]);
+        bnd = src.chunk_off[(int64_t)c + lane < nl ? (int64_t)c + lane : nl];
+    }
     const int64_t r = row_rec[g];
     const uint32_t k = (uint32_t)(g - row_off[r]);
     const uint32_t cnt = rec_cnt[r];
@@ -357,6 +397,74 @@ __device__ __forceinline__ void row_one(const RowParams &P, const uint32_t *__re
     }
 
     int32_t id[MR][4];
+    if constexpr (LISTS) {
+        // the row's ids are [rel0, rel1) of the record's, [t_first, t_last] of the call's, and lie
+        // at its positions [jlo, jhi); before them the opening frame, after them the closing one
+        const int64_t rel0 = base > P.n_pre ? base - P.n_pre : 0;
+        const int64_t rel1 = base + l - P.n_pre < (int64_t)cnt ? base + l - P.n_pre : (int64_t)cnt;
+        const int jlo = (int)(rel0 + P.n_pre - base), jhi = (int)(rel1 + P.n_pre - base);
+        // id index of position 256 m + 4 lane (+ w); a framing position's is never used
+        const uint32_t tb = t0 + (uint32_t)(base - P.n_pre) + 4u * (uint32_t)lane;
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) id[m][w] = 0;
+        if (rel0 < rel1) {  // (wave-uniform, as everything derived from g alone)
+            const uint32_t t_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t0 + (uint32_t)rel1 - 1u));
+            const uint16_t *__restrict__ lc = src.lists + (int64_t)c * STAGE;
+            if ((uint32_t)__builtin_amdgcn_readlane((int)bnd, 63) > t_last) {
+                uint32_t q[MR][4];  // boundaries at or below the id: its chunk is c + q
+#pragma unroll
+                for (int m = 0; m < MR; ++m)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) q[m][w] = 0;
+#pragma unroll 1
+                for (int b = 1; b < 64; ++b) {
+                    const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)bnd, b);
+                    if (x > t_last) break;
+#pragma unroll
+                    for (int m = 0; m < MR; ++m)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) q[m][w] += tb + 256u * m + w >= x ? 1u : 0u;
+                }
+#pragma unroll
+                for (int m = 0; m < MR; ++m)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const int j = 256 * m + 4 * lane + w;
+                        const uint32_t lo = (uint32_t)__shfl((int)bnd, (int)(q[m][w] & 63u));
+                        const uint32_t e = q[m][w] * (uint32_t)STAGE + (tb + 256u * m + w - lo);
+                        if (j >= jlo && j < jhi) id[m][w] = (int32_t)lc[e];
+                    }
+            } else {
+                // (one position of every lane a step; the selects keep id in registers)
+#pragma unroll 1
+                for (int i = 0; i < 4 * MR; ++i) {
+                    const int j = 256 * (i >> 2) + 4 * lane + (i & 3);
+                    const bool is_id = j >= jlo && j < jhi;
+                    int32_t v = 0;
+                    if (is_id) {
+                        const uint32_t t = tb + 256u * (uint32_t)(i >> 2) + (uint32_t)(i & 3);
+                        const int64_t cc = list_chunk_of(src.chunk_off, (int64_t)c, nl - 1, t);
+                        v = (int32_t)src.lists[list_slot(src.chunk_off, cc, t)];
+                    }
+#pragma unroll
+                    for (int m = 0; m < MR; ++m)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) id[m][w] = i == 4 * m + w && is_id ? v : id[m][w];
+                }
+            }
+        }
+        const int post0 = (int)(base - P.n_pre - (int64_t)cnt);  // (+ j: the closing frame's index)
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int j = 256 * m + 4 * lane + w;
+                if (j < l && j < jlo) id[m][w] = frame_id(P.pre, (int)base + j);
+                if (j < l && j >= jhi) id[m][w] = frame_id(P.post, post0 + j);
+            }
+    } else {
 #pragma unroll
     for (int m = 0; m < MR; ++m)
 #pragma unroll
@@ -366,11 +474,12 @@ __device__ __forceinline__ void row_one(const RowParams &P, const uint32_t *__re
             if (j < l) {
                 const int64_t f = base + j;
                 if (f < P.n_pre) v = frame_id(P.pre, (int)f);
-                else if (f < P.n_pre + (int64_t)cnt) v = (int32_t)tok[t0 + (f - P.n_pre)];
+                else if (f < P.n_pre + (int64_t)cnt) v = (int32_t)src.tok[t0 + (f - P.n_pre)];
                 else v = frame_id(P.post, (int)(f - P.n_pre - cnt));
             }
             id[m][w] = v;
         }
+    }
     if (RM1 && !mine) return;  // (the LATE pass's row)
     // attention: 0 on [S-l, S) when l < S (reversed-range quirk, bert_data.rs:58-63 / gpt_data.rs:33-41)
     const int tail0 = l < S ? S - l : S;
@@ -478,9 +587,7 @@ __device__ __forceinline__ void downstream_tiny(const SmallDown &d, const RowPar
     step();
     // (the records' loads before the compaction's stores: independent, in flight together)
     if (lane < R) record_one(P, off, lane, N, coff, n_chunks, d.rec_local, rtok, rcnt, rrows);
-    for (int64_t cb = 0; cb < n_chunks; cb += COMPACT_CPW)
-        compact_wave(cb, d.tokc, d.chunk_cnt, coff, n_chunks, d.tok, d.long_count, d.chunk_ent, d.long_list,
-                     d.long_scratch, d.long_pool, d.stride);
+    for (int64_t cb = 0; cb < n_chunks; cb += COMPACT_CPW) compact_small(d, cb, coff, n_chunks);
     step();
     uint32_t G;
     {
@@ -506,7 +613,7 @@ __device__ __forceinline__ void downstream_tiny(const SmallDown &d, const RowPar
         const uint32_t *const rrec = G <= (uint32_t)ROWS_LDS ? s_rrec : d.row_rec;
         const int64_t g_end = d.out.direct.cap ? (int64_t)G : ((int64_t)G + P.B - 1) / P.B * P.B;
         for (int64_t g = 0; g < g_end; ++g)
-            row_one<MR, false, false>(P, d.tok, rtok, rcnt, roff, rrec, g, (int64_t)G, d.out, nullptr, lane);
+            row_one<MR, false, false>(P, TokSrc{d.tok}, rtok, rcnt, roff, rrec, g, (int64_t)G, d.out, nullptr, lane);
     }
 }
 

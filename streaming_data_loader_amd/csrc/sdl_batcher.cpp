@@ -272,6 +272,7 @@ struct sdl_batcher {
     DevBuf<double> d_zig;  // span rng_mode 1: ZIG_NORM_X then ZIG_NORM_F (257 each)
 
     // per-call workspace
+    DevBuf<uint32_t> row_chunk;  // row -> the chunk of its first id (rows read from the chunk lists)
     DevBuf<uint32_t> ranges, tokc, chunk_cnt, chunk_off, rec_local, tok_ids, rec_tok, rec_cnt, rec_rows, row_off,
         row_rec, scan_tmp;
     DevBuf<int32_t> o_ids, o_am, o_tt, o_lab;
@@ -452,13 +453,17 @@ struct sdl_batcher {
         const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
         const int64_t rows_cap = rows_capacity(N, R);
         ranges.ensure((size_t)std::max<int64_t>(n_chunks, 1) * 3);
-        tokc.ensure((size_t)std::max<int64_t>(n_chunks, 1) * (dt.kind == TOK_UNIGRAM ? UNI_STAGE : STAGE));
+        // a chunk's list: STAGE u16 (WordPiece), STAGE / UNI_STAGE u32 entries (BPE / Unigram)
+        const bool wp = dt.kind != TOK_BYTE_BPE && dt.kind != TOK_UNIGRAM;
+        tokc.ensure((size_t)std::max<int64_t>(n_chunks, 1) * (dt.kind == TOK_UNIGRAM ? UNI_STAGE : wp ? STAGE / 2 : STAGE));
         chunk_cnt.ensure((size_t)n_chunks + 1);
         chunk_off.ensure((size_t)n_chunks + 1);
         rec_local.ensure((size_t)R + 1);
-        // ids <= text bytes for WordPiece/BPE; Unigram adds a "▁" piece per word
-        // and expanding normalizations: bound by the chunk entries + the pool
-        tok_ids.ensure(dt.kind == TOK_UNIGRAM ? (size_t)2 * N + 1024 * 1024 + 1 : (size_t)N + 1);
+        // the dense id array: ids <= text bytes for WordPiece/BPE; Unigram adds a "▁" piece per
+        // word and expanding normalizations: bound by the chunk entries + the pool.  (WordPiece
+        // mlm / clm / labels: only a small call needs it, below)
+        const size_t tok_ids_n = dt.kind == TOK_UNIGRAM ? (size_t)2 * N + 1024 * 1024 + 1 : (size_t)N + 1;
+        if (!wp || span()) tok_ids.ensure(tok_ids_n);
         rec_tok.ensure((size_t)R + 1);
         rec_cnt.ensure((size_t)R + 1);
         rec_rows.ensure((size_t)R + 1);
@@ -510,6 +515,12 @@ struct sdl_batcher {
             if (profiling) HIP_TRY(hipEventRecord(ev[i], st));
         };
         const bool small = !piped && !profiling && n_chunks <= SMALL_CHUNKS && R <= 8192;
+        // WordPiece, large calls: k_rows reads the chunk lists themselves -- no dense copy of the
+        // ids (span's rows kernels and the small-call kernels read the dense array)
+        const bool from_lists = wp && !small && !span();
+        if (!from_lists) tok_ids.ensure(tok_ids_n);
+        else row_chunk.ensure((size_t)std::max<int64_t>(rows_cap, 1));
+        uint16_t *const lists = reinterpret_cast<uint16_t *>(tokc.p);
         mark(0);
         // (one segment: k_chunk_ranges also writes its record bounds and zeroes the label error word)
         const bool fold = sc.K == 1 && n_chunks > 0;
@@ -558,7 +569,7 @@ struct sdl_batcher {
                         uni ? uni_counters.p : bpe ? long_count.p : nullptr,
                         uni || bpe ? chunk_ent.p : nullptr, bpe ? long_list.p : nullptr,
                         bpe ? long_scratch.p : nullptr, uni ? uni_pool.p : nullptr,
-                        uni ? (int64_t)UNI_STAGE : (int64_t)STAGE, rec_local.p, rec_tok.p, rec_cnt.p,
+                        uni ? (int64_t)UNI_STAGE : (int64_t)STAGE, wp ? 1 : 0, rec_local.p, rec_tok.p, rec_cnt.p,
                         rec_rows.p, row_off.p, row_rec.p, fused_done ? fuse_stat : nullptr,
                         uni ? uni_err.p : nullptr, 0, out};
             // mlm (Philox) / clm rows in the same workgroup, no k_rows launch
@@ -584,17 +595,21 @@ struct sdl_batcher {
             else if (bpe)
                 HIP_TRY(launch_compact_tokens(tokc.p, chunk_cnt.p, chunk_off.p, n_chunks, tok_ids.p, long_count.p,
                                               chunk_ent.p, long_list.p, long_scratch.p, s));
-            else
-                HIP_TRY(launch_compact_tokens(tokc.p + ca * STAGE, chunk_cnt.p + ca, chunk_off.p + ca, cz - ca,
-                                              tok_ids.p, nullptr, nullptr, nullptr, nullptr, s));
+            else if (!from_lists)
+                HIP_TRY(launch_compact_tokens(tokc.p + ca * (STAGE / 2), chunk_cnt.p + ca, chunk_off.p + ca, cz - ca,
+                                              tok_ids.p, nullptr, nullptr, nullptr, nullptr, s, nullptr, STAGE, true));
             if (!piped) mark(4);
             HIP_TRY(launch_records(p, d_off, R, N, chunk_off.p, n_chunks, rec_local.p, rec_tok.p, rec_cnt.p, rec_rows.p,
                                    sel, s));
             if (!piped) mark(5);
             if (piped) HIP_TRY(launch_scan_range(rec_rows.p, row_off.p, seg_rb.p, k, s));
             else HIP_TRY(launch_exclusive_scan(rec_rows.p, row_off.p, R, scan_tmp.p, s));
-            HIP_TRY(launch_row_map(row_off.p, R, row_rec.p, sel, s));
+            // (segment k's rows read lists and offsets of chunks < cz only: all written by now)
+            const RowChunkIn rc{row_chunk.p, rec_tok.p, rec_cnt.p, chunk_off.p, d_off, cz, P.S, P.n_pre, P.chunk};
+            HIP_TRY(launch_row_map(row_off.p, R, row_rec.p, sel, s, from_lists ? &rc : nullptr));
             }
+            const TokSrc src = from_lists ? TokSrc{nullptr, lists, chunk_off.p, cz, row_chunk.p}
+                                          : TokSrc{tok_ids.p, nullptr, nullptr, 0, nullptr};
             if (!piped) mark(6);
             if (span()) {
                 span_err.ensure(1);
@@ -617,9 +632,9 @@ struct sdl_batcher {
                 // (and walks the rows past the guess in a second pass)
                 if (rm1 && rec0) {
                     HIP_TRY(hipStreamWaitEvent(s, rand_ev[1], 0));
-                    HIP_TRY(launch_rows(p, tok_ids.p, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s));
+                    HIP_TRY(launch_rows(p, src, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s));
                 } else if (!rows_done) {
-                    HIP_TRY(launch_rows(p, tok_ids.p, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s));
+                    HIP_TRY(launch_rows(p, src, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s));
                 }
             }
             if (multi())
@@ -669,13 +684,13 @@ struct sdl_batcher {
                                       rec_local.p, long_count.p, long_list.p, cap, long_scratch.p, bpe_err.p, st));
             downstream(0, st);
         } else if (!piped) {
-            HIP_TRY(launch_wordpiece_chunks(dt, d_text, N, d_off, R, ranges.p, tokc.p, chunk_cnt.p, rec_local.p, st, 0,
+            HIP_TRY(launch_wordpiece_chunks(dt, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st, 0,
                                             -1));
             downstream(0, st);
         } else {
             ensure_pipe_events(sc.K);
             for (int k = 0; k < sc.K; ++k) {
-                HIP_TRY(launch_wordpiece_chunks(dt, d_text, N, d_off, R, ranges.p, tokc.p, chunk_cnt.p, rec_local.p, st,
+                HIP_TRY(launch_wordpiece_chunks(dt, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st,
                                                 sc.cb[k], sc.cb[k + 1]));
                 HIP_TRY(hipEventRecord(pipe_ev[k], st));
                 HIP_TRY(hipStreamWaitEvent(stream2, pipe_ev[k], 0));

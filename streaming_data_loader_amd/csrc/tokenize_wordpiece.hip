@@ -26,8 +26,10 @@
 //      hash of 4 dwords + one 32-B probe of the L2-resident vocab table whose
 //      slots hold the piece bytes inline; other words take a general path;
 //   5. staged ids (LDS, indexed by piece byte position: a piece never has
-//      more ids than bytes) are compacted into this chunk's slice of `tokc`,
-//      and each record boundary's local id offset is recorded.
+//      more ids than bytes) are compacted into this chunk's slice of `tokc`
+//      as a packed u16 list (STAGE slots a chunk), which the rows kernel reads
+//      as it lies (pipeline.hip, list_index.hpp), and each record boundary's
+//      local id offset is recorded.
 #include "common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
@@ -414,7 +416,7 @@ constexpr int WP_WAVES = 5;
 constexpr int WP_NPROBE = 2;
 __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_WAVES, 8))) void k_wordpiece_chunks(
     DevTok T, const uint8_t *__restrict__ text, int64_t N, const uint64_t *__restrict__ off, int64_t R,
-    const uint32_t *__restrict__ ranges, uint32_t *__restrict__ tokc, uint32_t *__restrict__ chunk_cnt,
+    const uint32_t *__restrict__ ranges, uint16_t *__restrict__ tokc, uint32_t *__restrict__ chunk_cnt,
     uint32_t *__restrict__ rec_local, int64_t c_begin) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[WIN];
     __shared__ uint32_t s_rbits[RBITS_WORDS + 1];
@@ -1053,13 +1055,18 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     for (int i = a0; i < a1; ++i) mine += s_cnt[i];
     uint32_t total;
     const uint32_t base0 = block_excl_sum<TOK_THREADS>(mine, &total, s_scratch);
-    uint32_t *dst = tokc + ci * STAGE;
+    uint16_t *dst = tokc + ci * STAGE;  // (a slice is STAGE u16 = 2304 B: 16-B aligned)
     uint32_t base = base0;
-    // non-temporal stores: the lists are read once, by the compaction, and must
-    // not evict the vocabulary table from L2 (rows 0.39 -> 0.34 ms measured).
     // The list is first packed in LDS (the text window is dead now) so the wave
-    // writes it as whole 16-B lanes: scattered 4-B non-temporal stores cost
-    // 3.5x the list's bytes in HBM writes (PMC WRITE_SIZE 851 MB vs 240 MB).
+    // writes it as whole 16-B lanes: scattered 4-B stores cost 3.5x the list's
+    // bytes in HBM writes (PMC WRITE_SIZE 851 MB vs 240 MB).  It is stored as it
+    // lies there, u16 (every id is below 65,536), 8 ids a lane; the last store's
+    // slots past `total` hold whatever the window held.  Plain stores, not
+    // non-temporal ones: the rows kernel reads the lists next and is bound by the
+    // latency of those loads, so the lists (0.1 GB a 256 MiB arena) should still
+    // be in the memory-side cache then (mlm rows 0.324 ms after non-temporal
+    // stores, 0.270 after plain ones; the tokenizer itself 1.118 -> 1.116 ms;
+    // profiles/r07/lists).
     if (total <= (uint32_t)(WIN / 2)) {
         lds_u16 *packed = (lds_u16 *)s_win;
         for (int i = a0; i < a1; ++i) {
@@ -1070,20 +1077,19 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
         }
         __syncthreads();
         const lds_u32 *p32 = (const lds_u32 *)s_win;
-        for (uint32_t e = 4u * (uint32_t)tid; e < total; e += 4u * TOK_THREADS) {
-            const uint32_t x = p32[e >> 1], y = p32[(e >> 1) + 1];
+        for (uint32_t e = 8u * (uint32_t)tid; e < total; e += 8u * TOK_THREADS) {
             u32x4 v;
-            v.x = x & 0xFFFFu;
-            v.y = x >> 16;
-            v.z = y & 0xFFFFu;
-            v.w = y >> 16;
-            __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(dst + e));
+            v.x = p32[e >> 1];
+            v.y = p32[(e >> 1) + 1];
+            v.z = p32[(e >> 1) + 2];
+            v.w = p32[(e >> 1) + 3];
+            *reinterpret_cast<u32x4 *>(dst + e) = v;
         }
     } else {
         for (int i = a0; i < a1; ++i) {
             const int prel = s_pieces[i] & 0xFFF;
             const int k = s_cnt[i];
-            for (int j = 0; j < k; ++j) __builtin_nontemporal_store((uint32_t)s_stage[prel + j], dst + base + j);
+            for (int j = 0; j < k; ++j) dst[base + j] = s_stage[prel + j];
             base += k;
         }
     }
@@ -1132,7 +1138,7 @@ void print_phase_cycles() {
 #endif
 
 hipError_t launch_wordpiece_chunks(const DevTok &T, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
-                                   uint32_t *ranges, uint32_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
+                                   uint32_t *ranges, uint16_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
                                    hipStream_t st, int64_t c_begin, int64_t c_end) {
     const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
     if (c_end < 0 || c_end > n_chunks) c_end = n_chunks;
