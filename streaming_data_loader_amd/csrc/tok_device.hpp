@@ -194,8 +194,9 @@ __device__ __forceinline__ uint32_t hash16(const W16 &c, uint32_t n, uint32_t co
     return hfinal(h);
 }
 
-// General probe: payload = w[start, end) of a byte buffer (any length).
-__device__ __forceinline__ int probe_general(const DevTok &T, const uint8_t *w, int start, int end, uint32_t cont) {
+// General probe: payload = w[start, end) of a byte buffer (any length; private, global or LDS).
+template <typename Buf>
+__device__ __forceinline__ int probe_general(const DevTok &T, const Buf *w, int start, int end, uint32_t cont) {
     const uint32_t n = (uint32_t)(end - start);
     uint32_t h = hinit(n, cont);
     W16 first{0, 0, 0, 0};

@@ -16,24 +16,38 @@
 //      in VGPRs) and stores them into an LDS window [c0-32, c0+1024+32);
 //      record starts in the window become an LDS bitmap;
 //   2. classification is register-resident: an arithmetic ASCII classifier
-//      packs 16 four-bit visible classes into one u64; only lead bytes >= 0xC0
-//      (two-level Unicode table in L2) and added-token openers take a loop;
-//   3. a wave scan carries the last visible class across lanes; piece starts
-//      (words, isolated chars, added tokens) are compacted into an LDS list;
+//      packs 16 four-bit visible classes into one u64.  A lead byte >= 0xC0 is
+//      looked up (two-level Unicode table in L2) by the lane that owns it and
+//      its class goes into that lane's registers; the lane's first lead is
+//      decoded from the window before the record bitmap exists, so its table
+//      load is in flight together with the record offsets' loads.  Added-token
+//      openers take a block-wide pass over an LDS list, which chunks without
+//      an opener skip;
+//   3. the state before the chunk comes from ballots over the 32 halo bytes
+//      (the serial walk only when a non-ASCII byte or a possible added token
+//      decides it), a wave scan carries the last visible class across lanes,
+//      and piece starts (words, isolated chars, added tokens) are compacted
+//      into an LDS list;
 //   4. each lane WordPiece-tokenizes pieces i, i+64, ...: an ASCII word of
 //      <= 16 bytes is read from LDS as 5 aligned dwords + v_alignbyte,
 //      lower-cased and classified with SWAR, and every candidate piece is one
 //      hash of 4 dwords + one 32-B probe of the L2-resident vocab table whose
-//      slots hold the piece bytes inline; other words take a general path;
+//      slots hold the piece bytes inline; other words take a general path
+//      (its byte buffers are LDS: the kernel uses no scratch memory);
 //   5. staged ids (LDS, indexed by piece byte position: a piece never has
 //      more ids than bytes) are compacted into this chunk's slice of `tokc`
 //      as a packed u16 list (STAGE slots a chunk), which the rows kernel reads
-//      as it lies (pipeline.hip, list_index.hpp), and each record boundary's
-//      local id offset is recorded.
+//      as it lies (pipeline.hip, list_index.hpp).  Lane t packs its own 16
+//      slots: a slot holds an id where a piece starts (the piece-start mask
+//      in its registers) unless the exception bitmap says otherwise -- a piece
+//      with more than one id, or none (wp_pack.hpp) -- and its list position
+//      is a wave sum plus a popcount.  Each record boundary's local id offset
+//      comes from the same sums, fetched from the owning lane by a shuffle.
 #include "common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
 #include "tok_device.hpp"
+#include "wp_pack.hpp"
 
 #include <cstdio>
 
@@ -83,6 +97,31 @@ __device__ __forceinline__ uint32_t vclass_of_entry(uint32_t e) {
     }
 }
 
+// decode() of the char at window index wi (arena position p) before the record-start bitmap
+// exists: the same result unless a record starts inside the sequence, which the caller
+// checks once it does.
+__device__ __forceinline__ uint32_t decode_spec(const lds_u8 *win, int wi, int64_t p, int64_t N, int *len) {
+    const uint32_t b = win[wi];
+    int n;
+    uint32_t c;
+    if ((b & 0xE0u) == 0xC0u) { n = 2; c = b & 0x1Fu; }
+    else if ((b & 0xF0u) == 0xE0u) { n = 3; c = b & 0x0Fu; }
+    else if ((b & 0xF8u) == 0xF0u) { n = 4; c = b & 0x07u; }
+    else { *len = 1; return 0xFFFDu; }
+    if (p + n > N) { *len = 1; return 0xFFFDu; }
+    for (int k = 1; k < n; ++k) {
+        const uint32_t x = win[wi + k];
+        if ((x & 0xC0u) != 0x80u) { *len = 1; return 0xFFFDu; }
+        c = (c << 6) | (x & 0x3Fu);
+    }
+    *len = n;
+    return c;
+}
+// Entry of a decoded char and, for a canonical BMP char, its precomputed one-char id in one load.
+__device__ __forceinline__ uint2 uentry2(const DevTok &T, uint32_t cp, int len) {
+    return (len == 2 && cp >= 0x80u) || (len == 3 && cp >= 0x800u) ? T.ubmp[cp] : make_uint2(uentry(T, cp), 0u);
+}
+
 // Full visible class of the char at q (general path).
 __device__ __forceinline__ uint32_t vclass_general(const Ctx &C, int64_t q) {
     const DevTok &T = *C.T;
@@ -108,8 +147,9 @@ __device__ __forceinline__ uint32_t vclass_general(const Ctx &C, int64_t q) {
 
 // ---- WordPiece ------------------------------------------------------------------
 
-// WordPiece::tokenize over a normalized word held in a byte buffer.
-__device__ __forceinline__ int wordpiece_general(const DevTok &T, const uint8_t *w, int L, lds_u16 *out) {
+// WordPiece::tokenize over a normalized word held in a byte buffer (LDS).
+template <typename Buf>
+__device__ __forceinline__ int wordpiece_general(const DevTok &T, const Buf *w, int L, lds_u16 *out) {
     int n = 0, start = 0;
     while (start < L) {
         const int lim = start == 0 ? T.maxlen_first : T.maxlen_cont;
@@ -214,10 +254,10 @@ __device__ __forceinline__ int word_materialize(const Ctx &C, int64_t p, int64_t
                 if (x + l1 >= nb) break;
                 const int l2 = utf8_len(buf[x + l1]);
                 if (ccc_at(x, l1) > ccc_at(x + l1, l2)) {
-                    uint8_t t[4];
-                    for (int k = 0; k < l1; ++k) t[k] = buf[x + k];
+                    uint32_t t = 0;  // (a char is at most 4 bytes)
+                    for (int k = 0; k < l1; ++k) t |= (uint32_t)buf[x + k] << (8 * k);
                     for (int k = 0; k < l2; ++k) buf[x + k] = buf[x + l1 + k];
-                    for (int k = 0; k < l1; ++k) buf[x + l2 + k] = t[k];
+                    for (int k = 0; k < l1; ++k) buf[x + l2 + k] = (uint8_t)(t >> (8 * k));
                     swapped = true;
                     x += l2;
                 } else {
@@ -284,16 +324,10 @@ __device__ __forceinline__ int word_materialize(const Ctx &C, int64_t p, int64_t
     return nb;
 }
 
-// General WORD piece materialized in private memory, WordPiece one probe at a
-// time (words whose normalization exceeds the LDS lattice buffer).
-__device__ __forceinline__ int word_general(const Ctx &C, int64_t p, int64_t rec_end, lds_u16 *out) {
-    int nchars, nbytes;
-    const int64_t i = word_extent(C, p, rec_end, &nchars, &nbytes);
-    if (nchars > MAX_WORD_CHARS) {
-        out[0] = (uint16_t)C.T->unk_id;
-        return 1;
-    }
-    uint8_t buf[MAX_WORD_BYTES];
+// General WORD piece [p, i) of at most MAX_WORD_CHARS normalized chars, materialized in
+// `buf` (LDS, MAX_WORD_BYTES), WordPiece one probe at a time (words whose normalization
+// exceeds the lattice's LW_MAX bytes).
+__device__ __forceinline__ int word_general(const Ctx &C, int64_t p, int64_t i, lds_u8 *buf, lds_u16 *out) {
     const int nb = word_materialize(C, p, i, buf);
     return wordpiece_general(*C.T, buf, nb, out);
 }
@@ -421,8 +455,10 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     __shared__ __attribute__((aligned(16))) uint8_t s_win[WIN];
     __shared__ uint32_t s_rbits[RBITS_WORDS + 1];
     __shared__ uint16_t s_pieces[CHUNK];   // (pos - c0) | kind << 12
-    __shared__ uint16_t s_stage[STAGE];    // ids staged at their piece's byte position
-    __shared__ uint8_t s_cnt[CHUNK];       // ids per piece
+    __shared__ __attribute__((aligned(16))) uint16_t s_stage[STAGE];  // ids staged at their piece's byte position
+    // per-byte class overrides of the rare pass (step 2); from step 4 on its first words are the
+    // exception bitmap of the stage slots (wp_pack.hpp)
+    __shared__ __attribute__((aligned(16))) uint8_t s_ovr[CHUNK];
     __shared__ uint16_t s_pend[PEND_CAP];  // pending piece indices (step 4b)
     __shared__ uint32_t s_scratch[TOK_THREADS / 64 + 3];
     // non-ASCII chars found by the rare pass: [0, 32) a WS/ISO char starts at the
@@ -458,6 +494,39 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     int64_t rb_next = rz <= R ? (int64_t)off[rz] : N;
     if (rb_next > N) rb_next = N;
     __syncthreads();
+    // ---- 2. register-resident classification of the lane's 16 bytes ----------
+    // (before the record-start bitmap, which only the lookups after it need)
+    const int64_t s0 = c0 + 16 * tid;
+    const int nown = s0 >= c1 ? 0 : (int)(c1 - s0 < 16 ? c1 - s0 : 16);
+    const int rel0 = HALO_L + 16 * tid;  // window index of s0 (multiple of 16)
+    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+    uint64_t cls = 0;
+    uint32_t leads = 0, opens = 0;
+    const uint32_t o4 = T.opener * 0x01010101u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t x = wv[j];
+        cls |= (uint64_t)vclass4(x) << (16 * j);
+        leads |= gather4(x & (x << 1)) << (4 * j);  // >= 0xC0
+        opens |= gather4(~nzb(x ^ o4)) << (4 * j);
+    }
+    if (!T.n_special) opens = 0;
+    if (nown < 16) {
+        cls &= nown ? ((1ull << (4 * nown)) - 1ull) : 0ull;
+        leads &= (1u << nown) - 1u;
+        opens &= (1u << nown) - 1u;
+    }
+    // Non-ASCII lead bytes (rare: a few a KiB of English text) are looked up by the lane that
+    // owns them: decode + two-level Unicode table, the class goes into the lane's own `cls`.
+    // The lane's first lead is decoded here, from the window alone, so that its table load is
+    // in flight together with the record offsets' loads below and not after their barrier.
+    const int l0 = leads ? __builtin_ctz(leads) : -1;
+    uint2 ue0 = make_uint2(0u, 0u);
+    int len0 = 1;
+    if (l0 >= 0) {
+        const uint32_t cp0 = decode_spec(win, rel0 + l0, s0 + l0, N, &len0);
+        ue0 = uentry2(T, cp0, len0);
+    }
     for (int k = tid; k < nrb; k += TOK_THREADS) {
         const int rel = (int)((int64_t)off[ra + k] - w0);
         atomicOr(&s_rbits[rel >> 5], 1u << (rel & 31));
@@ -477,79 +546,23 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     return;
 #endif
 
-    // ---- 2. register-resident classification of the lane's 16 bytes ----------
-    const int64_t s0 = c0 + 16 * tid;
-    const int nown = s0 >= c1 ? 0 : (int)(c1 - s0 < 16 ? c1 - s0 : 16);
-    const int rel0 = HALO_L + 16 * tid;  // window index of s0 (multiple of 16)
-    const uint32_t rmask = (rbits[rel0 >> 5] >> (rel0 & 31)) & 0xFFFFu;
-    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-    uint64_t cls = 0;
-    uint32_t leads = 0, opens = 0;
-    const uint32_t o4 = T.opener * 0x01010101u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t x = wv[j];
-        cls |= (uint64_t)vclass4(x) << (16 * j);
-        leads |= gather4(x & (x << 1)) << (4 * j);  // >= 0xC0
-        opens |= gather4(~nzb(x ^ o4)) << (4 * j);
-    }
-    if (!T.n_special) opens = 0;
-    if (nown < 16) {
-        cls &= nown ? ((1ull << (4 * nown)) - 1ull) : 0ull;
-        leads &= (1u << nown) - 1u;
-        opens &= (1u << nown) - 1u;
-    }
-    uint8_t *s_ovr = s_cnt;
-    *reinterpret_cast<uint4 *>(s_ovr + 16 * tid) = make_uint4(~0u, ~0u, ~0u, ~0u);
-    // Rare bytes are classified block-parallel, one per thread, and returned as
-    // per-byte class overrides in LDS (s_cnt doubles as the override array and
-    // s_pieces as the work list until the pieces are found):
-    //   (a) non-ASCII lead bytes: decode + two-level Unicode table;
-    //   (b) added tokens: every opener byte that starts a match marks its bytes
-    //       (SPEC at the start, invisible after); applied after (a).
-    // tid 0 also owns openers in [c0 - max_special_len + 1, c0): a token starting
-    // there may cover this chunk's first bytes
-    uint32_t opens_left = 0;
-    if (T.n_special && tid == 0) {
-        for (int d = 1; d < T.max_special_len; ++d)
-            if (c0 - d >= 0 && C.byte(c0 - d) == T.opener) opens_left |= 1u << (d - 1);
-    }
-    uint32_t nrare;
-    const uint32_t rare_n = (uint32_t)__builtin_popcount(leads) |
-                            ((uint32_t)(__builtin_popcount(opens) + __builtin_popcount(opens_left)) << 16);
-    const uint32_t rbase = block_excl_sum<TOK_THREADS>(rare_n, &nrare, s_scratch);
-    const uint32_t n_leads = nrare & 0xFFFFu, n_opens = nrare >> 16;
-    {
-        uint32_t lb = rbase & 0xFFFFu, ob = n_leads + (rbase >> 16);
-        for (uint32_t m = leads; m;) {
-            const int i = __builtin_ctz(m);
-            m &= m - 1;
-            s_pieces[lb++] = (uint16_t)(HALO_L + 16 * tid + i);
+    // record starts at the lane's bytes and the 16 after them
+    const uint32_t rm32 = (uint32_t)((((uint64_t)rbits[(rel0 >> 5) + 1] << 32) | rbits[rel0 >> 5]) >> (rel0 & 31));
+    const uint32_t rmask = rm32 & 0xFFFFu;
+    for (uint32_t m = leads; m; m &= m - 1) {
+        const int i = __builtin_ctz(m);
+        const int wi = rel0 + i, rel = 16 * tid + i;
+        int len = len0;
+        uint2 ue = ue0;
+        // every other lead, and a first lead with a record start inside its sequence (never in
+        // valid text), through the checked decode
+        if (i != l0 || ((rm32 >> (i + 1)) & ((1u << (len0 - 1)) - 1u)) != 0u) {
+            const uint32_t cp = decode(C, w0 + wi, win[wi], &len);
+            ue = uentry2(T, cp, len);
         }
-        for (uint32_t m = opens; m;) {
-            const int i = __builtin_ctz(m);
-            m &= m - 1;
-            s_pieces[ob++] = (uint16_t)(HALO_L + 16 * tid + i);
-        }
-        for (uint32_t m = opens_left; m;) {
-            const int d = __builtin_ctz(m) + 1;
-            m &= m - 1;
-            s_pieces[ob++] = (uint16_t)(HALO_L - d);
-        }
-    }
-    __syncthreads();
-    PHASE_STAMP(2);
-    for (uint32_t k = tid; k < n_leads; k += TOK_THREADS) {
-        const int wi = s_pieces[k];
-        const int rel = wi - HALO_L;
-        int len;
-        const uint32_t cp = decode(C, w0 + wi, win[wi], &len);
-        // (a canonical BMP char: its entry and its precomputed one-char id in one load)
-        const uint2 ue = (len == 2 && cp >= 0x80u) || (len == 3 && cp >= 0x800u) ? T.ubmp[cp]
-                                                                                 : make_uint2(uentry(T, cp), 0u);
         const uint32_t e = ue.x;
         const uint32_t vc = vclass_of_entry(e);
-        s_ovr[rel] = (uint8_t)vc;
+        cls = (cls & ~(0xFull << (4 * i))) | ((uint64_t)vc << (4 * i));
         if (vc == V_WS || vc == V_ISO) atomicOr(&s_nabits[rel >> 5], 1u << (rel & 31));
         // an ISO char is a piece of its own: when it normalizes to one char of <= 16
         // bytes, its WordPiece is one probe of that char (no "##" piece can start
@@ -574,9 +587,29 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
         }
     }
     PHASE_STAMP(12);
-    if (n_opens) {  // block-uniform
+    // Added tokens: every opener byte that starts a match marks its bytes (SPEC at the start,
+    // invisible after) as per-byte class overrides in LDS, one opener per thread from a work
+    // list in s_pieces (free until the pieces are found); applied after the leads' classes.
+    // tid 0 also owns openers in [c0 - max_special_len + 1, c0) (a ballot over the halo's
+    // bytes): a token starting there may cover this chunk's first bytes.  Chunks without an opener skip all of it.
+    static_assert(TOK_THREADS == 64, "__any() is the block's vote");
+    // the left halo, lane j < 32: byte c0 - 1 - j (also the look-back's, below)
+    const bool in_halo = tid < HALO_L;
+    const uint32_t hb = in_halo ? win[HALO_L - 1 - tid] : 0u;
+    const uint64_t halo_open = T.n_special ? __ballot(in_halo && hb == T.opener) : 0ull;
+    const uint32_t opens_left =
+        tid == 0 && T.max_special_len > 1 ? (uint32_t)halo_open & ((1u << (T.max_special_len - 1)) - 1u) : 0u;
+    static_assert(MAX_SPECIAL_LEN <= HALO_L, "an added token that covers the chunk's first byte starts in the halo");
+    if (__any((opens | opens_left) != 0u)) {
+        *reinterpret_cast<uint4 *>(s_ovr + 16 * tid) = make_uint4(~0u, ~0u, ~0u, ~0u);
+        uint32_t n_opens;
+        uint32_t ob = block_excl_sum<TOK_THREADS>((uint32_t)(__builtin_popcount(opens) + __builtin_popcount(opens_left)),
+                                                  &n_opens, s_scratch);
+        for (uint32_t m = opens; m; m &= m - 1) s_pieces[ob++] = (uint16_t)(rel0 + __builtin_ctz(m));
+        for (uint32_t m = opens_left; m; m &= m - 1) s_pieces[ob++] = (uint16_t)(HALO_L - (__builtin_ctz(m) + 1));
         __syncthreads();
-        for (uint32_t k = n_leads + tid; k < n_leads + n_opens; k += TOK_THREADS) {
+        PHASE_STAMP(2);
+        for (uint32_t k = tid; k < n_opens; k += TOK_THREADS) {
             const int wi = s_pieces[k];
             const int64_t x = w0 + wi;
             const int m = special_match(C, x);
@@ -587,10 +620,7 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                 if (y >= c0 && y < c1) s_ovr[y - c0] = (uint8_t)(j == 0 ? V_SPEC : V_NONE);
             }
         }
-    }
-    __syncthreads();
-    PHASE_STAMP(3);
-    {
+        __syncthreads();
         const uint4 o = *reinterpret_cast<const uint4 *>(s_ovr + 16 * tid);
         const uint32_t ov[4] = {o.x, o.y, o.z, o.w};
         uint64_t onib = 0, keep = 0;  // override classes, nibbles without one (0xFF)
@@ -601,6 +631,7 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
         }
         cls = (cls & keep) | (onib & ~keep);
     }
+    PHASE_STAMP(3);
     // Each byte's previous visible class, byte-parallel: a record start at byte
     // i + 1 puts a stopper (8) at byte i, then the visible classes and stoppers
     // fill forward over the invisible bytes in four doubling steps.
@@ -618,23 +649,53 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     // lane summary for the carry scan: 0 = pass-through, 0x100 | v = state after
     const uint32_t last = (uint32_t)(fill >> 60);
     const uint32_t summ = (last != 0u || (rmask & 1u)) ? 0x100u | (last & 7u) : 0u;
-    // state before the chunk: last visible char of the same record before c0
-    if (tid == 0) {
-        uint32_t st = V_NONE;
-        int64_t q = c0 - 1;
-        while (q >= 0 && !C.rstart(q + 1)) {
-            int64_t cs = q;
-            int k = 0;
-            while (k < 3 && cs > 0 && (C.byte(cs) & 0xC0u) == 0x80u && !C.rstart(cs)) { --cs; ++k; }
-            const uint32_t vc = vclass_general(C, cs);
-            if (vc != V_NONE) { st = vc; break; }
-            q = cs - 1;
+    // state before the chunk: last visible char of the same record before c0.  Lanes 0-31
+    // each take one byte of the left halo (lane j: byte c0 - 1 - j); ballots give the visible
+    // ASCII bytes, the record starts and the bytes only the general classifier can judge -- a
+    // byte >= 0x80, or one an added token could cover or start: an opener at it or within
+    // max_special_len - 1 bytes before it, or that range leaving the halo.  The state is the
+    // class of the nearest visible byte unless a record start comes first; a general byte in
+    // the deciding range, or a halo without either, takes the serial walk (wave-uniform).
+    uint32_t chunk_state;
+    {
+        const uint32_t hvc = ascii_vclass(hb & 0x7Fu);
+        const int ri = HALO_L - (in_halo ? tid : 0);  // window index of the byte after
+        const uint64_t rsm = __ballot(in_halo && ((rbits[ri >> 5] >> (ri & 31)) & 1u));
+        const uint64_t vism = __ballot(in_halo && hb < 0x80u && hvc != V_NONE);
+        uint64_t gen = __ballot(in_halo && hb >= 0x80u);
+        if (T.n_special) {
+            const int msl = T.max_special_len;
+            for (int d = 0; d < msl && d < HALO_L; ++d) gen |= halo_open >> d;
+            gen |= msl > HALO_L ? ~0ull : ~0ull << (HALO_L + 1 - msl);
         }
-        s_scratch[TOK_THREADS / 64] = st;
+        const int jr = rsm ? __builtin_ctzll(rsm) : 64, jv = vism ? __builtin_ctzll(vism) : 64;
+        bool fast;
+        if (jr <= jv) {  // a record start ends the search before anything visible
+            fast = jr < 64 && (gen & ((1ull << jr) - 1ull)) == 0ull;
+            chunk_state = V_NONE;
+        } else {
+            fast = (gen & ((2ull << jv) - 1ull)) == 0ull;
+            chunk_state = lane_bcast(hvc, jv);
+        }
+        if (!fast) {
+            if (tid == 0) {
+                uint32_t st = V_NONE;
+                int64_t q = c0 - 1;
+                while (q >= 0 && !C.rstart(q + 1)) {
+                    int64_t cs = q;
+                    int k = 0;
+                    while (k < 3 && cs > 0 && (C.byte(cs) & 0xC0u) == 0x80u && !C.rstart(cs)) { --cs; ++k; }
+                    const uint32_t vc = vclass_general(C, cs);
+                    if (vc != V_NONE) { st = vc; break; }
+                    q = cs - 1;
+                }
+                s_scratch[TOK_THREADS / 64] = st;
+            }
+            __syncthreads();
+            chunk_state = s_scratch[TOK_THREADS / 64];
+            __syncthreads();
+        }
     }
-    __syncthreads();
-    const uint32_t chunk_state = s_scratch[TOK_THREADS / 64];
-    __syncthreads();
     PHASE_STAMP(4);
     const uint32_t st_in = block_excl_last_scan<TOK_THREADS>(summ, s_scratch);
 
@@ -677,6 +738,17 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     // (a) and (b) alternate in rounds so the pending list stays within
     // PEND_CAP (a round of (a) adds at most TOK_THREADS * TOK_UNROLL).
     lds_u16 *stage = (lds_u16 *)s_stage;
+    // exceptions to "a piece has one id, in its first byte's slot" (wp_pack.hpp): the pending
+    // walk sets the bit of every further id as it stages it (and clears them if the word ends
+    // as [UNK]), the other paths set a finished piece's bits at once; the overrides were consumed barriers ago
+    uint32_t *s_vx = reinterpret_cast<uint32_t *>(s_ovr);
+    static_assert(4 * WP_VX_WORDS <= CHUNK && WP_VX_WORDS <= TOK_THREADS && WP_SLOTS == STAGE && WP_MAIN == CHUNK, "");
+    if (tid < WP_VX_WORDS) s_vx[tid] = 0u;
+    auto stage_count = [&](int prel, int n) {
+        if (n == 1) return;
+        const WpRange r = wp_exception_range(prel, n);
+        for (int wd = r.lo >> 5; wd <= (r.hi - 1) >> 5; ++wd) atomicOr(&s_vx[wd], wp_word_mask(wd, r.lo, r.hi));
+    };
     if (tid == 0) {
         s_scratch[TOK_THREADS / 64 + 1] = 0;  // pending count
         s_scratch[TOK_THREADS / 64 + 2] = 0;  // deferred count
@@ -741,16 +813,12 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
             if (kind == V_SPEC) {
                 const int m = special_match(C, c0 + prel);
                 stage[prel] = (uint16_t)T.special_id[m < 0 ? 0 : m];
-                s_cnt[pi] = 1;
             } else if (kind == V_ISO) {
                 const uint32_t b = win[prel + HALO_L];
                 if (b < 0x80u) {
                     stage[prel] = (uint16_t)T.ascii_id[b];
-                    s_cnt[pi] = 1;
-                } else if ((s_nabits[CHUNK / 32 + (prel >> 5)] >> (prel & 31)) & 1u) {
-                    s_cnt[pi] = 1;  // its id is in its stage slot (rare pass)
-                } else {
-                    pend[u] = true;
+                } else if (!((s_nabits[CHUNK / 32 + (prel >> 5)] >> (prel & 31)) & 1u)) {
+                    pend[u] = true;  // (else its id is in its stage slot: rare pass)
                 }
             } else {
                 W16 lw;
@@ -776,7 +844,6 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                 const int id = probe_result(pr[u], key[u], cand[u]);
                 if (id >= 0) {
                     stage[prel_u[u]] = (uint16_t)id;
-                    s_cnt[pi] = 1;
                 } else {
                     pend[u] = true;
                 }
@@ -847,19 +914,11 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                             active = end > 0;
                             if (!active && gl == 0) {  // no piece can match: the word is [UNK]
                                 out[0] = (uint16_t)T.unk_id;
-                                s_cnt[pi] = 1;
                             }
                         } else if (gl == 0) {
-                            if (kind == V_ISO) {
-                                int len;
-                                const uint32_t e = uentry(T, decode(C, p, win[prel + HALO_L], &len));
-                                uint8_t buf[16];
-                                const int nb = append_norm(C, e, p, len, buf, 0);
-                                s_cnt[pi] = (uint8_t)wordpiece_general(T, buf, nb, out);
-                            } else {  // deferred to the cooperative lattice below
-                                const uint32_t d = atomicAdd(&s_scratch[TOK_THREADS / 64 + 2], 1u);
-                                s_pend[d] = (uint16_t)pi;  // d < this round's consumed entries
-                            }
+                            // deferred to (c) below: the cooperative lattice, or the general ISO char
+                            const uint32_t d = atomicAdd(&s_scratch[TOK_THREADS / 64 + 2], 1u);
+                            s_pend[d] = (uint16_t)pi;  // d < this round's consumed entries
                         }
                     }
                 }
@@ -909,11 +968,13 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                 const int n1 = e1 - start;
                 lds_u16 *out = stage + prel;
                 if (id >= 0) {
-                    if (gl == 0) out[nout] = (uint16_t)id;
+                    if (gl == 0) {
+                        out[nout] = (uint16_t)id;
+                        if (nout) atomicOr(&s_vx[(prel + nout) >> 5], 1u << ((prel + nout) & 31));  // a further id
+                    }
                     ++nout;
                     start += got;
                     if (start >= L) {
-                        if (gl == 0) s_cnt[pi] = (uint8_t)nout;
                         active = false;
                     } else {
                         end = L < start + T.maxlen_cont ? L : start + T.maxlen_cont;
@@ -924,7 +985,8 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                     if (end <= start) {  // no piece matches here: the whole word is [UNK]
                         if (gl == 0) {
                             out[0] = (uint16_t)T.unk_id;
-                            s_cnt[pi] = 1;
+                            for (int wd = (prel + 1) >> 5; nout > 1 && wd <= (prel + nout - 1) >> 5; ++wd)
+                                atomicAnd(&s_vx[wd], ~wp_word_mask(wd, prel + 1, prel + nout));  // its staged ids
                         }
                         active = false;
                     }
@@ -933,13 +995,16 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
         }
         // (c) deferred words (normalization longer than 16 bytes, DEL runs,
         //     canonical ordering): one at a time, normalized by lane 0 into LDS
-        //     (the pending list's space, free now), then the WordPiece lattice:
+        //     (the pending list's space, free now: PEND_CAP u16 hold the
+        //     MAX_WORD_BYTES of the longest word), then the WordPiece lattice:
         //     every (start, length) candidate with a vocab piece of that length
         //     is one probe task dealt across the wave, and each start keeps its
         //     longest hit (atomic max of length << 16 | id); lane 0 walks
         //     greedy longest-match-first over them.  Probe latencies per word
         //     ~ candidates / 64, where probing one candidate at a time pays one
-        //     per candidate.
+        //     per candidate.  An ISO char whose normalization is longer than 16
+        //     bytes comes here too: lane 0 probes it one candidate at a time.
+        static_assert(MAX_WORD_BYTES <= 2 * PEND_CAP && LW_BUF + 4 * LW_MAX <= 2 * PEND_CAP, "s_pend holds the word");
         __syncthreads();
         const int ndef = (int)s_scratch[TOK_THREADS / 64 + 2];
         if (ndef) {
@@ -963,15 +1028,19 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                 const int64_t dp = c0 + dprel;
                 lds_u16 *dout = stage + dprel;
                 int dL = 0;
-                if (lane == 0) {
+                if (lane == 0 && (s_pieces[dpi] >> 12) == V_ISO) {
+                    int len;
+                    const uint32_t e = uentry(T, decode(C, dp, win[dprel + HALO_L], &len));
+                    const int nb = append_norm(C, e, dp, len, wb, 0);
+                    stage_count(dprel, wordpiece_general(T, wb, nb, dout));
+                } else if (lane == 0) {
                     const int64_t rend = rec_end_of(C, rb_next, dp);
                     int nch, nby;
                     const int64_t iend = word_extent(C, dp, rend, &nch, &nby);
                     if (nch > MAX_WORD_CHARS) {
                         dout[0] = (uint16_t)T.unk_id;
-                        s_cnt[dpi] = 1;
                     } else if (nby > LW_MAX || T.wp_long_pieces) {
-                        s_cnt[dpi] = (uint8_t)word_general(C, dp, rend, dout);
+                        stage_count(dprel, word_general(C, dp, iend, wb, dout));
                     } else {
                         dL = word_materialize(C, dp, iend, wb);
                         for (int k = dL; k < dL + 20; ++k) wb[k] = 0;
@@ -1032,7 +1101,7 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                         dout[0] = (uint16_t)T.unk_id;
                         nout = 1;
                     }
-                    s_cnt[dpi] = (uint8_t)nout;
+                    stage_count(dprel, nout);
                 }
                 __syncthreads();
             }
@@ -1048,15 +1117,18 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     PHASE_STAMP(7);
 
     // ---- 5. compact ids into this chunk's tokc slice ------------------------------
-    const int per = (np + TOK_THREADS - 1) / TOK_THREADS;
-    const int a0 = tid * per < np ? tid * per : np;
-    const int a1 = a0 + per < np ? a0 + per : np;
-    uint32_t mine = 0;
-    for (int i = a0; i < a1; ++i) mine += s_cnt[i];
-    uint32_t total;
-    const uint32_t base0 = block_excl_sum<TOK_THREADS>(mine, &total, s_scratch);
+    // Lane t packs the ids of its own stage slots [16t, 16t + 16) -- lanes 0-7 also the tail
+    // slots [CHUNK + 16t, ...), which only the chunk's last word reaches.  A slot holds an id
+    // where a piece starts (pmask, still in registers) or the exception bitmap says otherwise
+    // (wp_pack.hpp); a slot's list position is a wave sum plus a popcount.  No walk over the
+    // piece list, no per-piece counts.
+    const uint32_t vmain = pmask ^ wp_bits16(s_vx, 16 * tid);
+    const uint32_t vtail = tid < WP_TAIL_LANES ? wp_bits16(s_vx, CHUNK + 16 * tid) : 0u;
+    uint32_t tot2;
+    const uint32_t ex2 = block_excl_sum<TOK_THREADS>(wp_lane_counts(vmain, vtail), &tot2, s_scratch);
+    const uint32_t total = wp_total(tot2);
+    const uint32_t base = wp_main_base(ex2);
     uint16_t *dst = tokc + ci * STAGE;  // (a slice is STAGE u16 = 2304 B: 16-B aligned)
-    uint32_t base = base0;
     // The list is first packed in LDS (the text window is dead now) so the wave
     // writes it as whole 16-B lanes: scattered 4-B stores cost 3.5x the list's
     // bytes in HBM writes (PMC WRITE_SIZE 851 MB vs 240 MB).  It is stored as it
@@ -1069,11 +1141,21 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     // profiles/r07/lists).
     if (total <= (uint32_t)(WIN / 2)) {
         lds_u16 *packed = (lds_u16 *)s_win;
-        for (int i = a0; i < a1; ++i) {
-            const int prel = s_pieces[i] & 0xFFF;
-            const int k = s_cnt[i];
-            for (int j = 0; j < k; ++j) packed[base + j] = s_stage[prel + j];
-            base += k;
+        // 16 unconditional 2-B stores a lane, no loop and no branch: a slot without an id goes
+        // to a per-lane dump slot in the pending list's space (dead now)
+        lds_u16 *dump = (lds_u16 *)s_pend + tid;
+        auto pack16 = [&](const uint16_t *slots, uint32_t valid, uint32_t b0) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(slots), b = *reinterpret_cast<const uint4 *>(slots + 8);
+            const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                lds_u16 *to = (valid >> i) & 1u ? packed + wp_pos(b0, valid, i) : dump;
+                *to = (uint16_t)(w[i >> 1] >> (16 * (i & 1)));
+            }
+        };
+        pack16(s_stage + 16 * tid, vmain, base);
+        if (tot2 >> 16) {  // block-uniform
+            if (tid < WP_TAIL_LANES) pack16(s_stage + CHUNK + 16 * tid, vtail, wp_tail_base(ex2, tot2));
         }
         __syncthreads();
         const lds_u32 *p32 = (const lds_u32 *)s_win;
@@ -1085,38 +1167,27 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
             v.w = p32[(e >> 1) + 3];
             *reinterpret_cast<u32x4 *>(dst + e) = v;
         }
-    } else {
-        for (int i = a0; i < a1; ++i) {
-            const int prel = s_pieces[i] & 0xFFF;
-            const int k = s_cnt[i];
-            for (int j = 0; j < k; ++j) dst[base + j] = s_stage[prel + j];
-            base += k;
-        }
+    } else {  // more ids than the window holds (runs of punctuation): straight to the slice
+        uint32_t b0 = base;
+        for (uint32_t m = vmain; m; m &= m - 1) dst[b0++] = s_stage[16 * tid + __builtin_ctz(m)];
+        b0 = wp_tail_base(ex2, tot2);
+        for (uint32_t m = vtail; m; m &= m - 1) dst[b0++] = s_stage[CHUNK + 16 * tid + __builtin_ctz(m)];
     }
-    __syncthreads();
-    // the stage is free now: it holds each piece's id offset in the chunk
-    uint16_t *s_poff = s_stage;
-    base = base0;
-    for (int i = a0; i < a1; ++i) {
-        s_poff[i] = (uint16_t)base;
-        base += s_cnt[i];
-    }
-    __syncthreads();
     PHASE_STAMP(8);
     if (tid == 0) chunk_cnt[ci] = total;
-    // record boundaries owned by this chunk: local id offset of the first piece
-    // at or after the boundary
+    // record boundaries owned by this chunk: ids of the chunk before the boundary, from the
+    // base and the valid mask of the lane that owns the boundary's byte.  The loop is
+    // wave-uniform (every lane serves the shuffles).
     const int k_lo = (int)(r_lo - ra);
-    for (int k = k_lo + tid; k < nrb; k += TOK_THREADS) {
-        const int64_t pos = (int64_t)off[ra + k];
-        if (pos >= c1) break;
-        const int rel = (int)(pos - c0);
-        int lo = 0, hi = np;
-        while (lo < hi) {
-            const int m = (lo + hi) >> 1;
-            if ((int)(s_pieces[m] & 0xFFF) < rel) lo = m + 1; else hi = m;
-        }
-        rec_local[ra + k] = lo < np ? (uint32_t)s_poff[lo] : total;
+    for (int k0 = k_lo; k0 < nrb; k0 += TOK_THREADS) {
+        const int k = k0 + tid;
+        const int64_t pos = k < nrb ? (int64_t)off[ra + k] : c1;
+        const bool own = pos >= c0 && pos < c1;
+        const int rel = own ? (int)(pos - c0) : 0;
+        const uint32_t lb = (uint32_t)__shfl((int)base, wp_boundary_lane(rel));
+        const uint32_t lv = (uint32_t)__shfl((int)vmain, wp_boundary_lane(rel));
+        if (own) rec_local[ra + k] = wp_boundary_offset(lb, lv, rel);
+        if (!__any(own)) break;  // (offsets ascend)
     }
     PHASE_STAMP(9);
 }
@@ -1125,7 +1196,7 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
 void print_phase_cycles() {
     unsigned long long h[16];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(sdl_phase_cycles), sizeof(h)) != hipSuccess) return;
-    static const char *names[] = {"", "load+rbits", "classify+lists", "rare-openers+sync", "merge+lookback",
+    static const char *names[] = {"", "load+classify+rbits", "opener-list", "openers", "fill+lookback",
                                   "scan+pieces", "-", "wp-pending", "compact", "rec_local", "wp-init",
                                   "wp-first-probes", "rare-leads"};
     unsigned long long tot = 0;
