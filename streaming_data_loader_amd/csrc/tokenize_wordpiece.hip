@@ -28,12 +28,22 @@
 //      decides it), a wave scan carries the last visible class across lanes,
 //      and piece starts (words, isolated chars, added tokens) are compacted
 //      into an LDS list;
-//   4. each lane WordPiece-tokenizes pieces i, i+64, ...: an ASCII word of
-//      <= 16 bytes is read from LDS as 5 aligned dwords + v_alignbyte,
-//      lower-cased and classified with SWAR, and every candidate piece is one
-//      hash of 4 dwords + one 32-B probe of the L2-resident vocab table whose
-//      slots hold the piece bytes inline; other words take a general path
-//      (its byte buffers are LDS: the kernel uses no scratch memory);
+//   4. byte-level work is done once per byte, not once per piece: every lane
+//      writes the 16 bits of its own bytes into two LDS bitmaps over the chunk
+//      and 16 bytes of its right halo (wp_extent.hpp) -- S, where a run of
+//      ASCII letters and digits stops (any other byte, a record start, the
+//      text's end), and F, the stops a fast word may end at (ASCII whitespace
+//      or punctuation, a non-ASCII whitespace / punctuation lead the rare pass
+//      found, a record start, the text's end) -- from the classes of step 2.
+//      Each lane then WordPiece-tokenizes pieces i, i+64, ...: a word's length
+//      is a count of trailing zeros in S's window behind its first byte and
+//      its fast flag one bit of F's, both windows from one LDS read; an ASCII
+//      word of <= 16 bytes is read from LDS as 5 aligned dwords + v_alignbyte
+//      and lower-cased by `| 0x20` under a byte mask (inside the length every
+//      byte is a letter or digit), and every candidate piece is one hash of 4
+//      dwords + one 32-B probe of the L2-resident vocab table whose slots hold
+//      the piece bytes inline; other words take a general path (its byte
+//      buffers are LDS: the kernel uses no scratch memory);
 //   5. staged ids (LDS, indexed by piece byte position: a piece never has
 //      more ids than bytes) are compacted into this chunk's slice of `tokc`
 //      as a packed u16 list (STAGE slots a chunk), which the rows kernel reads
@@ -47,6 +57,7 @@
 #include "device_util.hpp"
 #include "kernels.hpp"
 #include "tok_device.hpp"
+#include "wp_extent.hpp"
 #include "wp_pack.hpp"
 
 #include <cstdio>
@@ -457,7 +468,8 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     __shared__ uint16_t s_pieces[CHUNK];   // (pos - c0) | kind << 12
     __shared__ __attribute__((aligned(16))) uint16_t s_stage[STAGE];  // ids staged at their piece's byte position
     // per-byte class overrides of the rare pass (step 2); from step 4 on its first words are the
-    // exception bitmap of the stage slots (wp_pack.hpp)
+    // exception bitmap of the stage slots (wp_pack.hpp) and, behind it, the stop and
+    // fast-terminator bitmaps of the chunk's bytes (wp_extent.hpp)
     __shared__ __attribute__((aligned(16))) uint8_t s_ovr[CHUNK];
     __shared__ uint16_t s_pend[PEND_CAP];  // pending piece indices (step 4b)
     __shared__ uint32_t s_scratch[TOK_THREADS / 64 + 3];
@@ -502,11 +514,17 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
     uint64_t cls = 0;
     uint32_t leads = 0, opens = 0;
+    // the ASCII classes step 4's bitmaps need, kept from here (one register; classifying the 16
+    // bytes again there costs more): bits 0-15 WS or ISO, 16-31 letter or digit
+    uint32_t sfm = 0;
+    static_assert(V_OTHER == WX_V_OTHER && V_WS == WX_V_WS && V_ISO == WX_V_ISO && V_NONE == 0, "");
     const uint32_t o4 = T.opener * 0x01010101u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t x = wv[j];
-        cls |= (uint64_t)vclass4(x) << (16 * j);
+        const uint32_t n4 = vclass4(x);
+        cls |= (uint64_t)n4 << (16 * j);
+        sfm |= wx_nibble_classes(n4) << (4 * j);
         leads |= gather4(x & (x << 1)) << (4 * j);  // >= 0xC0
         opens |= gather4(~nzb(x ^ o4)) << (4 * j);
     }
@@ -744,6 +762,36 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     uint32_t *s_vx = reinterpret_cast<uint32_t *>(s_ovr);
     static_assert(4 * WP_VX_WORDS <= CHUNK && WP_VX_WORDS <= TOK_THREADS && WP_SLOTS == STAGE && WP_MAIN == CHUNK, "");
     if (tid < WP_VX_WORDS) s_vx[tid] = 0u;
+    // Stop and fast-terminator bitmaps of the chunk's bytes and the first 16 of the right halo
+    // (wp_extent.hpp), behind the exception bitmap: every lane writes the 16 bits of its own
+    // bytes, lane 0 also those of bits CHUNK .. CHUNK + 15.  Words of S and F alternate, so
+    // lane t's halves are u16 (t & 1) of u32 words 2 (t >> 1) and 2 (t >> 1) + 1.
+    static_assert(4 * WP_VX_WORDS % 8 == 0 && 4 * WP_VX_WORDS + 8 * WX_WORDS <= CHUNK && WX_CHUNK == CHUNK &&
+                      HALO_L + WX_BITS <= WIN,
+                  "the bitmaps lie in s_ovr; their halo bits have bytes and record bits in the window");
+    const lds_u64 *sf64 = (const lds_u64 *)(s_ovr + 4 * WP_VX_WORDS);
+    {
+        lds_u16 *sf16 = (lds_u16 *)(s_ovr + 4 * WP_VX_WORDS);
+        lds_u32 *sf32 = (lds_u32 *)(s_ovr + 4 * WP_VX_WORDS);
+        const WxStops own = wx_stops_from(sfm >> 16, sfm, rmask, wp_bits16(s_nabits, 16 * tid), nown);
+        sf16[4 * (tid >> 1) + (tid & 1)] = (uint16_t)own.s;
+        sf16[4 * (tid >> 1) + 2 + (tid & 1)] = (uint16_t)own.f;
+        // the halo's 16 bytes, one a lane, by two ballots (no lane owns them, and a branch for
+        // one lane would cost the wave a whole classification)
+        const bool in16 = tid < WX_BITS - WX_CHUNK;
+        const uint32_t hb16 = win[HALO_L + CHUNK + (tid & 15)];
+        const uint32_t han = (uint32_t)__ballot(in16 && wx_is_alnum(hb16));
+        const uint32_t htm = (uint32_t)__ballot(in16 && wx_is_term(hb16));
+        const int64_t left = N - (c0 + CHUNK);
+        const WxStops halo = wx_stops_from(han, htm, wp_bits16(rbits, HALO_L + CHUNK), 0u,
+                                           left < 0 ? 0 : left < 16 ? (int)left : 16);
+        if (tid == 0) {
+            sf32[2 * (CHUNK / 32)] = halo.s;
+            sf32[2 * (CHUNK / 32) + 1] = halo.f;
+            sf32[2 * (CHUNK / 32) + 2] = 0u;
+            sf32[2 * (CHUNK / 32) + 3] = 0u;
+        }
+    }
     auto stage_count = [&](int prel, int n) {
         if (n == 1) return;
         const WpRange r = wp_exception_range(prel, n);
@@ -757,37 +805,25 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     PHASE_STAMP(10);
     const int lane = tid & 63;
     const lds_u32 *w32 = (const lds_u32 *)s_win;
-    // word setup shared by (a) and (b): returns false if the general path is needed
+    // word setup shared by (a) and (b): the word's length and fast flag from the two bitmaps
+    // (both windows come with one read, next to the window's five dwords), its bytes
+    // lower-cased by one OR -- inside the length every byte is an ASCII letter or digit;
+    // returns false if the general path is needed
     auto word_setup = [&](int prel, W16 &lw, int &Lout) -> bool {
         const int wr = prel + HALO_L;
         const int a = wr >> 2;
         const uint32_t sh = (uint32_t)(wr & 3);
+        const int q = prel + 1;
         const uint32_t x0 = w32[a], x1 = w32[a + 1], x2 = w32[a + 2], x3 = w32[a + 3], x4 = w32[a + 4];
+        const uint64_t e0 = sf64[q >> 5], e1 = sf64[(q >> 5) + 1];  // {S, F} words
         const W16 raw{__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh),
                       __builtin_amdgcn_alignbyte(x3, x2, sh), __builtin_amdgcn_alignbyte(x4, x3, sh)};
-        const uint32_t b16 = (x4 >> (8 * sh)) & 0xFFu;  // byte at p + 16
-        const uint32_t om = msb4(swar_alnum(raw.x)) | (msb4(swar_alnum(raw.y)) << 4) |
-                            (msb4(swar_alnum(raw.z)) << 8) | (msb4(swar_alnum(raw.w)) << 12);
-        int Lw = __builtin_ctz(~om);  // leading ASCII letters/digits, <= 16
-        const int rb0 = wr + 1;     // a record start at p+1 .. p+16 ends the word
-        const uint64_t rw = ((uint64_t)rbits[(rb0 >> 5) + 1] << 32) | rbits[rb0 >> 5];
-        const uint32_t rbm = (uint32_t)(rw >> (rb0 & 31)) & 0xFFFFu;
-        const int Lr = rbm ? __builtin_ctz(rbm) + 1 : 17;
-        bool fast;
-        if (Lr <= Lw) {
-            Lw = Lr;
-            fast = true;
-        } else {
-            const uint32_t t =
-                Lw < 16 ? (((Lw < 4 ? raw.x : Lw < 8 ? raw.y : Lw < 12 ? raw.z : raw.w) >> (8 * (Lw & 3))) & 0xFFu) : b16;
-            const uint32_t tc = vclass4(t) & 0xFu;  // t >= 0x80: V_NONE
-            const int te = prel + Lw;  // a non-ASCII WS/ISO char there ends the word too
-            const uint32_t na = t >= 0xC0u && te < CHUNK ? (s_nabits[te >> 5] >> (te & 31)) & 1u : 0u;
-            fast = (((0x6u >> tc) & 1u) | na) != 0u || c0 + prel + Lw >= N;  // WS, ISO
-        }
-        lw = keep_bytes(W16{swar_lower(raw.x), swar_lower(raw.y), swar_lower(raw.z), swar_lower(raw.w)}, Lw);
-        Lout = Lw;
-        return fast;
+        const WxExtent ex = wx_extent(wx_window((uint32_t)e0, (uint32_t)e1, q),
+                                      wx_window((uint32_t)(e0 >> 32), (uint32_t)(e1 >> 32), q), raw.x);
+        const WxMask m = wx_lower_keep(raw.x, raw.y, raw.z, raw.w, ex.len);
+        lw = W16{m.x, m.y, m.z, m.w};
+        Lout = ex.len;
+        return ex.fast;
     };
     for (int r0 = 0; r0 < np;) {
     // (a) batched first probes
