@@ -101,6 +101,34 @@ static bool cuckoo_insert(std::vector<VSlot> &tab, uint32_t mask, VSlot v) {
     return false;
 }
 
+// The first-piece table (wp_first.hpp) over the de-duplicated entries of the general table:
+// the non-"##" pieces of at most WF_MAXLEN bytes.  Every piece it holds is looked up again
+// through the functions the kernel uses.
+static void build_first_table(HostTokenizer &t, const std::vector<VSlot> &entries) {
+    std::vector<WfPiece> list;
+    t.first_maxlen = 0;
+    for (const VSlot &v : entries) {
+        const int n = (int)(v.key & 0xFFu);
+        const uint8_t *pay = t.vpool.data() + v.pool_off;  // (the pool is complete: no pointer moves)
+        if ((v.key >> 8) != 0u || !wf_fits(pay, n)) continue;
+        list.push_back(WfPiece{pay, n, (uint32_t)v.id});
+        t.first_maxlen = std::max(t.first_maxlen, n);
+    }
+    std::vector<std::vector<WfSlot>> tries;
+    WfSlot *tab = nullptr;
+    t.first_mask = wf_build(list.data(), (uint32_t)list.size(),
+                            [&](uint32_t n) {
+                                tries.emplace_back(n, WfSlot{{0, 0, 0, 0}});
+                                return tries.back().data();
+                            },
+                            &t.first_seed, &tab);
+    if (!t.first_mask) throw std::runtime_error("first-piece table build failed");
+    t.first_slots.assign(tab, tab + t.first_mask + 1);
+    for (const WfPiece &p : list)
+        if (wf_lookup(t.first_slots.data(), t.first_mask, t.first_seed, p.payload, p.n) != (int)p.id)
+            throw std::runtime_error("first-piece table: a piece is not found with its id");
+}
+
 static void build_vocab_table(HostTokenizer &t) {
     const size_t n = t.pieces.size();
     if (n > 65535) throw std::runtime_error("vocabulary larger than 65535 ids is not supported (u16 staging)");
@@ -133,6 +161,7 @@ static void build_vocab_table(HostTokenizer &t) {
         entries.push_back(v);
     }
     t.vpool.resize(t.vpool.size() + 64, 0);
+    build_first_table(t, entries);
     uint32_t slots = 1;
     while (slots < 4 * entries.size()) slots <<= 1;  // load <= 0.25
     for (;; slots <<= 1) {

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "wp_first.hpp"
 
 namespace sdl {
 
@@ -34,6 +35,10 @@ struct HostTokenizer {
     int maxlen_first = 0, maxlen_cont = 0;
     std::vector<uint8_t> wp_lens[2];  // WordPiece: distinct payload lengths <= LW_MAX (non-"##", "##")
     bool wp_long_pieces = false;      // a payload longer than LW_MAX exists
+    // WordPiece: the non-"##" pieces of <= WF_MAXLEN bytes again, in 16-byte slots (wp_first.hpp)
+    std::vector<WfSlot> first_slots;
+    uint32_t first_mask = 0, first_seed = 0;
+    int first_maxlen = 0;             // longest payload in it
     uint32_t opener = 0;
     int max_special_len = 0;
 

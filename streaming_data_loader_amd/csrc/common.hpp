@@ -23,7 +23,11 @@ constexpr int HALO_L = 32;                        // look-back bytes staged in L
 constexpr int HALO_R = 32;                        // look-ahead bytes staged in LDS
 constexpr int WIN = HALO_L + CHUNK + HALO_R;      // 1088 bytes of text in LDS
 constexpr int STAGE = CHUNK + 128;                // token slots per chunk (>= tokens owned)
-constexpr int TOK_UNROLL = 2;        // first probes in flight per lane (2: no spills at 5 waves/SIMD)
+// first probes in flight per lane: 4, so a round takes 256 pieces and most chunks (about 206
+// pieces on the fixture, 231 on held-out text) one round; two 16-B loads a probe (wp_first.hpp)
+// keep that at 95 VGPRs, no scratch, 5 waves/SIMD.  3 measured slower than 2 (two rounds a chunk
+// either way, more registers live); profiles/r10/first_table
+constexpr int TOK_UNROLL = 4;
 constexpr int PEND_CAP = 256;            // WordPiece pieces pending the state machine (LDS)
 constexpr int RB_CAP = 256;                       // record starts listed in LDS per window
 constexpr int MAX_WORD_CHARS = 100;               // WordPiece max_input_chars_per_word
@@ -77,6 +81,7 @@ __host__ __device__ inline uint32_t cuckoo_slot2(uint32_t h, uint32_t mask) {
     return g & mask;
 }
 static_assert(sizeof(VSlot) == 32, "VSlot must be 32 bytes");
+static_assert(TOK_THREADS * TOK_UNROLL <= PEND_CAP, "a round of first probes fits the pending list");
 static_assert(PEND_CAP % 64 == 0 && 2 * PEND_CAP >= LW_BUF + 4 * LW_MAX, "the WordPiece lattice buffer reuses the pending list");
 
 // Byte-level BPE merge table (cuckoo, 2 slots of 8 B): key = left id << 16 |
@@ -191,6 +196,16 @@ struct DevTok {
     int32_t maxlen_word;     // longest word-table payload
     int32_t maxlen_piece;    // longest piece, "▁" included (bytes)
     const uint8_t *upfx;     // longest plain piece (>= 4 B) under each hashed 4-byte prefix (uni_pfx_key)
+};
+
+// The WordPiece chunk kernel's first-piece table (wp_first.hpp), a kernel argument of its own:
+// every tokenize kernel takes DevTok by value, and a field more in it moved the other
+// tokenizers' arguments and with them their scalar loads and register allocation (span measured
+// 0.04 ms a step slower; profiles/r10/first_table).
+struct DevFirst {
+    const uint4 *slots;      // non-"##" pieces of <= maxlen bytes in 16-B slots
+    uint32_t mask, seed;
+    int32_t maxlen;          // longest payload in the table (<= 14)
 };
 
 // Unigram prefix bound: a plain piece of >= 4 bytes starting with bytes x (little-endian u32) is

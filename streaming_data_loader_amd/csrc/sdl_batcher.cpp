@@ -247,6 +247,7 @@ struct sdl_batcher {
     RowParams P{};
     HostTokenizer tok;
     DevTok dt{};
+    DevFirst dfirst{};
     hipStream_t stream = nullptr;
     int device = 0;
 
@@ -257,6 +258,7 @@ struct sdl_batcher {
     DevBuf<VSlot> d_slots, d_wslots;
     DevBuf<int32_t> d_ascii_id;
     DevBuf<uint8_t> d_wp_lens;
+    DevBuf<WfSlot> d_first_slots;
     DevBuf<uint16_t> d_gpage, d_byte_id;
     DevBuf<uint8_t> d_gblock;
     DevBuf<MSlot> d_mslots;
@@ -684,13 +686,13 @@ struct sdl_batcher {
                                       rec_local.p, long_count.p, long_list.p, cap, long_scratch.p, bpe_err.p, st));
             downstream(0, st);
         } else if (!piped) {
-            HIP_TRY(launch_wordpiece_chunks(dt, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st, 0,
+            HIP_TRY(launch_wordpiece_chunks(dt, dfirst, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st, 0,
                                             -1));
             downstream(0, st);
         } else {
             ensure_pipe_events(sc.K);
             for (int k = 0; k < sc.K; ++k) {
-                HIP_TRY(launch_wordpiece_chunks(dt, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st,
+                HIP_TRY(launch_wordpiece_chunks(dt, dfirst, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st,
                                                 sc.cb[k], sc.cb[k + 1]));
                 HIP_TRY(hipEventRecord(pipe_ev[k], st));
                 HIP_TRY(hipStreamWaitEvent(stream2, pipe_ev[k], 0));
@@ -1165,6 +1167,13 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             d.wp_lens = h->d_wp_lens.p;
         }
         d.wp_long_pieces = t.wp_long_pieces ? 1 : 0;
+        if (t.kind == TOK_WORDPIECE) {
+            h->d_first_slots.ensure(t.first_slots.size());
+            HIP_TRY(hipMemcpy(h->d_first_slots.p, t.first_slots.data(), t.first_slots.size() * sizeof(WfSlot),
+                              hipMemcpyHostToDevice));
+            h->dfirst = DevFirst{reinterpret_cast<const uint4 *>(h->d_first_slots.p), t.first_mask, t.first_seed,
+                                 t.first_maxlen};
+        }
         d.ascii_id = h->d_ascii_id.p;
         d.n_special = (int)t.added.size();
         d.max_special_len = t.max_special_len;

@@ -5,6 +5,7 @@
 
 #include "common.hpp"
 #include "device_util.hpp"
+#include "wp_first.hpp"
 
 namespace sdl {
 namespace {
@@ -192,6 +193,21 @@ __device__ __forceinline__ uint32_t hash16(const W16 &c, uint32_t n, uint32_t co
     h = hmix(h, c.z);
     h = hmix(h, c.w);
     return hfinal(h);
+}
+
+// First-piece table (wp_first.hpp): both slots of a candidate of <= F.maxlen bytes (zero
+// padded), two independent 16-B loads; then its id or -1: exact.
+struct FirstProbe {
+    uint4 a, b;
+};
+__device__ __forceinline__ FirstProbe first_probe_load(const DevFirst &F, const W16 &c) {
+    const uint32_t h = wf_hash(c.x, c.y, c.z, c.w, F.seed);
+    return FirstProbe{F.slots[wf_slot1(h, F.mask)], F.slots[wf_slot2(h, F.mask)]};
+}
+__device__ __forceinline__ int first_probe_result(const FirstProbe &P, const W16 &c) {
+    const int ra = wf_match(P.a.x, P.a.y, P.a.z, P.a.w, c.x, c.y, c.z, c.w);
+    const int rb = wf_match(P.b.x, P.b.y, P.b.z, P.b.w, c.x, c.y, c.z, c.w);
+    return ra >= 0 ? ra : rb;
 }
 
 // General probe: payload = w[start, end) of a byte buffer (any length; private, global or LDS).

@@ -40,10 +40,14 @@
 //      its fast flag one bit of F's, both windows from one LDS read; an ASCII
 //      word of <= 16 bytes is read from LDS as 5 aligned dwords + v_alignbyte
 //      and lower-cased by `| 0x20` under a byte mask (inside the length every
-//      byte is a letter or digit), and every candidate piece is one hash of 4
-//      dwords + one 32-B probe of the L2-resident vocab table whose slots hold
-//      the piece bytes inline; other words take a general path (its byte
-//      buffers are LDS: the kernel uses no scratch memory);
+//      byte is a letter or digit).  Its first probe, the whole word, reads the
+//      first-piece table (wp_first.hpp: the non-"##" pieces of <= 14 bytes in
+//      16-byte slots, 1 MiB for a 30 K vocabulary): a three-multiply hash of its
+//      4 dwords and two 16-B loads; a word that misses there or is longer goes to
+//      the pending walk, where every candidate piece is one hash of 4 dwords +
+//      one 32-B probe of the general vocab table whose slots hold the piece bytes
+//      inline; other words take a general path (its byte buffers are LDS: the
+//      kernel uses no scratch memory);
 //   5. staged ids (LDS, indexed by piece byte position: a piece never has
 //      more ids than bytes) are compacted into this chunk's slice of `tokc`
 //      as a packed u16 list (STAGE slots a chunk), which the rows kernel reads
@@ -460,7 +464,7 @@ constexpr int WP_WAVES = 5;
 // machine is bound by its lanes' probe latency, not by its step count.
 constexpr int WP_NPROBE = 2;
 __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_WAVES, 8))) void k_wordpiece_chunks(
-    DevTok T, const uint8_t *__restrict__ text, int64_t N, const uint64_t *__restrict__ off, int64_t R,
+    DevTok T, DevFirst F, const uint8_t *__restrict__ text, int64_t N, const uint64_t *__restrict__ off, int64_t R,
     const uint32_t *__restrict__ ranges, uint16_t *__restrict__ tokc, uint32_t *__restrict__ chunk_cnt,
     uint32_t *__restrict__ rec_local, int64_t c_begin) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[WIN];
@@ -746,15 +750,19 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
 
     // ---- 4. tokenize pieces ---------------------------------------------------------
     // (a) every lane sets up TOK_UNROLL pieces at a time and issues their
-    //     full-word probes back to back, so most words (in-vocabulary, <= 16 B)
-    //     finish with one latency and TOK_UNROLL loads in flight per lane;
+    //     full-word probes of the first-piece table back to back, so most words
+    //     (in-vocabulary, <= 14 B) finish with one latency and 2 * TOK_UNROLL
+    //     loads in flight per lane -- all of a chunk's first probes in one
+    //     flight unless it holds more than TOK_THREADS * TOK_UNROLL pieces;
     //     added tokens and one-byte punctuation finish without a probe;
     // (b) the rest (misses, collisions, longer or non-ASCII words) go to a
     //     pending list that a per-lane state machine drains: lanes pull work
     //     from a block-wide LDS queue and advance one vocab probe per iteration,
     //     so no lane idles behind a long word.
     // (a) and (b) alternate in rounds so the pending list stays within
-    // PEND_CAP (a round of (a) adds at most TOK_THREADS * TOK_UNROLL).
+    // PEND_CAP: a round of (a) adds at most TOK_THREADS * TOK_UNROLL = PEND_CAP,
+    // so it is admitted only while nothing is pending, and a chunk of more
+    // pieces alternates between (a) and (b).
     lds_u16 *stage = (lds_u16 *)s_stage;
     // exceptions to "a piece has one id, in its first byte's slot" (wp_pack.hpp): the pending
     // walk sets the bit of every further id as it stages it (and clears them if the word ends
@@ -829,16 +837,13 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     // (a) batched first probes
     for (; r0 < np && (int)s_scratch[TOK_THREADS / 64 + 1] <= PEND_CAP - TOK_THREADS * TOK_UNROLL;
          r0 += TOK_THREADS * TOK_UNROLL) {
-        uint32_t hsh[TOK_UNROLL], key[TOK_UNROLL];
         W16 cand[TOK_UNROLL];
-        int prel_u[TOK_UNROLL], L_u[TOK_UNROLL];
+        int prel_u[TOK_UNROLL];
         bool probe[TOK_UNROLL], pend[TOK_UNROLL];
 #pragma unroll
         for (int u = 0; u < TOK_UNROLL; ++u) {
             const int pi = r0 + u * TOK_THREADS + tid;
             probe[u] = pend[u] = false;
-            hsh[u] = key[u] = 0;
-            L_u[u] = 0;
             cand[u] = W16{0, 0, 0, 0};
             prel_u[u] = 0;
             if (pi >= np) continue;
@@ -859,25 +864,22 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
             } else {
                 W16 lw;
                 int Lw;
-                if (word_setup(prel, lw, Lw) && Lw <= T.maxlen_first) {
+                if (word_setup(prel, lw, Lw) && Lw <= F.maxlen) {
                     cand[u] = lw;
-                    L_u[u] = Lw;
-                    key[u] = (uint32_t)Lw;
-                    hsh[u] = hash16(lw, (uint32_t)Lw, 0u);
                     probe[u] = true;
                 } else {
                     pend[u] = true;
                 }
             }
         }
-        Probe pr[TOK_UNROLL];
+        FirstProbe pr[TOK_UNROLL];
 #pragma unroll
-        for (int u = 0; u < TOK_UNROLL; ++u) pr[u] = probe_load(T, hsh[u]);
+        for (int u = 0; u < TOK_UNROLL; ++u) pr[u] = first_probe_load(F, cand[u]);
 #pragma unroll
         for (int u = 0; u < TOK_UNROLL; ++u) {
             const int pi = r0 + u * TOK_THREADS + tid;
             if (probe[u]) {
-                const int id = probe_result(pr[u], key[u], cand[u]);
+                const int id = first_probe_result(pr[u], cand[u]);
                 if (id >= 0) {
                     stage[prel_u[u]] = (uint16_t)id;
                 } else {
@@ -1244,14 +1246,14 @@ void print_phase_cycles() {
 }
 #endif
 
-hipError_t launch_wordpiece_chunks(const DevTok &T, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
+hipError_t launch_wordpiece_chunks(const DevTok &T, const DevFirst &F, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
                                    uint32_t *ranges, uint16_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
                                    hipStream_t st, int64_t c_begin, int64_t c_end) {
     const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
     if (c_end < 0 || c_end > n_chunks) c_end = n_chunks;
     if (c_begin < 0) c_begin = 0;
     if (c_end <= c_begin) return hipSuccess;
-    hipLaunchKernelGGL(k_wordpiece_chunks, dim3((unsigned)(c_end - c_begin)), dim3(TOK_THREADS), 0, st, T, text, N,
+    hipLaunchKernelGGL(k_wordpiece_chunks, dim3((unsigned)(c_end - c_begin)), dim3(TOK_THREADS), 0, st, T, F, text, N,
                        off, R, ranges, tokc, chunk_cnt, rec_local, c_begin);
     return hipGetLastError();
 }
