@@ -32,6 +32,8 @@
 extern "C" {
 #endif
 
+/* 9 still: sdl_zstd_split_frames and sdl_zstd_inflate_device were added without changing any
+ * existing call or struct (an additive change keeps the version). */
 #define SDL_ABI_VERSION 9
 
 enum {
@@ -43,7 +45,7 @@ enum {
     SDL_ERR_NODEV = -5,       /* no HIP device: the product never falls back to the CPU */
     SDL_ERR_STATE = -6,       /* call out of order */
     SDL_ERR_CAPACITY = -7,    /* input larger than one call supports (>= 4 GiB of text) */
-    SDL_ERR_DATA = -8         /* corrupt input the reference's unwrap() panics on (gzip) */
+    SDL_ERR_DATA = -8         /* corrupt input the reference's unwrap() panics on (gzip, zstd) */
 };
 
 /* TaskType -> DataSet selection (rust/src/config.rs:20-62). */
@@ -215,7 +217,7 @@ int sdl_json_text_device(sdl_batcher *h, const uint8_t *d_jsonl, uint64_t len, v
 typedef struct sdl_inflated {
     uint8_t *d_out;             /* device, 16-byte aligned, 32 zero bytes after out_bytes */
     uint32_t *d_member_out;     /* device [n_members + 1]: member m's output is [d_member_out[m], [m+1]) */
-    int32_t *d_status;          /* device [n_members]: 0 ok, else a GZ_* reason code */
+    int32_t *d_status;          /* device [n_members]: 0 ok, else a GZ_* or ZS_* code */
     uint64_t out_bytes;
     uint64_t n_members;
     uint64_t n_bad;             /* members that failed */
@@ -243,6 +245,42 @@ int sdl_gzip_inflate_first_device(sdl_batcher *h, const uint8_t *d_gz, uint64_t 
  * member of a file).  offsets gets *n_members + 1 entries (capacity `cap`
  * entries; SDL_ERR_CAPACITY with *n_members set when too small). */
 int sdl_gzip_split_members(const uint8_t *gz, uint64_t len, uint64_t *offsets, uint64_t cap, uint64_t *n_members);
+
+/* ---- Provider step: zstd frame decode on the device ------------------------
+ * Replaces the ZstdDecoder under the provider's lines (zstd_file_provider.rs,
+ * general_file_provider.rs:96-115: the .jsonl.zst datasets and the .json.zst cache):
+ * every Zstandard frame (RFC 8878) in `d_zst` is decoded, all blocks of all frames
+ * at once for the entropy stages.  Frame f is bytes [d_frame_offsets[f],
+ * d_frame_offsets[f+1]) of d_zst (device, u64[n + 1]) -- what sdl_zstd_split_frames
+ * returns for a file.  The output reuses sdl_inflated with frames in the place of
+ * members: frame f's bytes are [d_member_out[f], d_member_out[f+1]) of d_out, back
+ * to back (d_out 16-byte aligned, 32 zero bytes after); a skippable frame has zero
+ * bytes and status 0.  d_zst is device memory, 16-byte aligned, zst_len < 4 GiB,
+ * total output < 4 GiB.  A bad frame makes the call return SDL_ERR_DATA with its
+ * index and reason in sdl_last_error(); per-frame ZS_* codes stay readable in
+ * d_status, the good frames of the call are still decoded (a frame that failed
+ * before its size was known has zero bytes, one that failed later -- offset
+ * before the frame's start, checksum -- keeps its extent with undefined bytes).
+ * A frame with a non-zero Dictionary_ID is refused: there are no dictionaries on
+ * this path.  The XXH64 content checksum is verified where a frame carries one,
+ * as libzstd does, unless SDL_ZSTD_NO_CHECKSUM is set in `flags`.  The buffers
+ * are owned by the handle until the next call; the call synchronises `stream`.
+ *
+ * Reference semantics: async-compression's ZstdDecoder with multiple_members off
+ * stops after the first frame (the generic decoder state machine it shares with
+ * GzipDecoder), so the reference-exact call passes only the range of a file's
+ * first non-skippable frame: offsets {o[k], o[k+1]} of sdl_zstd_split_frames. */
+#define SDL_ZSTD_NO_CHECKSUM 1u
+int sdl_zstd_inflate_device(sdl_batcher *h, const uint8_t *d_zst, uint64_t zst_len, const uint64_t *d_frame_offsets,
+                            uint64_t n_frames, uint32_t flags, void *stream, sdl_inflated *out);
+
+/* Host only (no GPU): the byte range of every frame of one .zst file, skippable
+ * frames included, from the frame headers and the 3-byte block headers alone (no
+ * entropy decode).  offsets gets *n_frames + 1 entries (capacity `cap` entries;
+ * SDL_ERR_CAPACITY with *n_frames set when too small).  Bytes that are no frame
+ * (bad magic, a reserved header bit, block type 3, a block over its maximum size,
+ * truncation) return SDL_ERR_DATA. */
+int sdl_zstd_split_frames(const uint8_t *zst, uint64_t len, uint64_t *offsets, uint64_t cap, uint64_t *n_frames);
 
 /* ---- Transport step: batches as serde_pickle frames on the device ----------
  * Replaces serde_pickle::to_vec(&dataset, Default::default()) of each finished
@@ -332,8 +370,8 @@ sdl_batcher *sdl_multi_handle(sdl_multi *m, uint32_t k);
  * `stream` (NULL = the handle's stream); returns when the copy is complete. */
 int sdl_device_to_host(sdl_batcher *h, void *dst, const void *src, size_t bytes, void *stream);
 
-/* Per-stage device time (ms) of the last sdl_process_device call, measured with
- * hipEvents on the stream the kernels ran on, when enabled. */
+/* Per-stage device time (ms) of the last sdl_process_device or sdl_zstd_inflate_device
+ * call, measured with hipEvents on the stream the kernels ran on, when enabled. */
 int sdl_set_profiling(sdl_batcher *h, int enable);
 int sdl_stage_times(sdl_batcher *h, const char **names, float *ms, int cap);
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "zstd_format.hpp"
 
 namespace sdl {
 
@@ -190,6 +191,52 @@ hipError_t launch_gz_crc_fold(const uint32_t *crc, const uint32_t *shift, uint64
 int64_t scan_tmp_words(int64_t n);
 hipError_t launch_exclusive_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *tmp, hipStream_t st,
                                  const uint32_t *carry_in = nullptr);
+
+// zstd.hip: Zstandard frames -> their bytes back to back (the provider's ZstdDecoder).  Per-frame
+// status (ZS_*, the codes of zstd_format.hpp); the output of frame f is [ooff[f], ooff[f + 1]).
+enum : int32_t {
+    ZS_OK = zs::OK,
+    ZS_E_RANGE = zs::E_RANGE,        // frame range outside the buffer, out of order, or not exactly one frame
+    ZS_E_TRUNC = zs::E_TRUNC,        // input ends inside the frame
+    ZS_E_MAGIC = zs::E_MAGIC,        // not a zstd frame, or a reserved header bit
+    ZS_E_DICT = zs::E_DICT,          // Dictionary_ID present and non-zero
+    ZS_E_WINDOW = zs::E_WINDOW,      // window log or offset code beyond the supported limit (31)
+    ZS_E_BTYPE = zs::E_BTYPE,        // block type 3
+    ZS_E_BSIZE = zs::E_BSIZE,        // block size over Block_Maximum_Size
+    ZS_E_LITHDR = zs::E_LITHDR,      // literals section header / stream sizes
+    ZS_E_HUF = zs::E_HUF,            // Huffman tree description (or treeless literals with no tree before)
+    ZS_E_FSE = zs::E_FSE,            // FSE table description
+    ZS_E_SEQHDR = zs::E_SEQHDR,      // sequences section header (or a Repeat_Mode with nothing to repeat)
+    ZS_E_ENDBITS = zs::E_ENDBITS,    // a bitstream did not end exactly
+    ZS_E_FAR = zs::E_FAR,            // offset before the frame's start
+    ZS_E_SIZE = zs::E_SIZE,          // decoded size != Frame_Content_Size
+    ZS_E_CHECKSUM = zs::E_CHECKSUM,  // XXH64 content checksum mismatch
+    ZS_E_STALL = zs::E_STALL         // a bounded loop ran out (a guard)
+};
+// Stage 1 (lane per frame): blocks == null counts the blocks of frame f into nblk[f]; otherwise
+// fills frames[f] and its block records from first_block[f] on (block_cap records in all).
+hipError_t launch_zs_index(const uint8_t *zst, uint64_t len, const uint64_t *foff, uint64_t n, zs::Frame *frames,
+                           zs::Block *blocks, const uint32_t *first_block, uint32_t *nblk, uint32_t block_cap,
+                           hipStream_t st);
+// Stage 2 (lane per block) and stage 3 (lane per frame; the frames' literal / sequence totals).
+hipError_t launch_zs_parse(const uint8_t *zst, const zs::Frame *frames, zs::Block *blocks, uint32_t nb, hipStream_t st);
+// totals (64-bit sums, so a call is refused before a 32-bit scan could wrap): [0] literal bytes,
+// [1] sequence records (k_zs_link), [2] output bytes (k_zs_chain)
+hipError_t launch_zs_link(zs::Frame *frames, zs::Block *blocks, uint64_t n, uint32_t *lit_tot, uint32_t *seq_tot,
+                          unsigned long long *totals, hipStream_t st);
+// Stage 4 (wave per block): tables, literals into the literal arena, sequence records, maps.
+hipError_t launch_zs_decode(const uint8_t *zst, const zs::Frame *frames, zs::Block *blocks, uint32_t nb,
+                            const uint32_t *lit_base, const uint32_t *seq_base, uint8_t *lit, zs::SeqRec *seq,
+                            hipStream_t st);
+// Stage 5 (lane per frame): incoming histories, block bases, the frames' output sizes.
+hipError_t launch_zs_chain(zs::Frame *frames, zs::Block *blocks, uint64_t n, uint32_t *out_size,
+                           unsigned long long *totals, hipStream_t st);
+// Stage 6 (workgroup per block), 7 (workgroup per frame), 8 (4 lanes per frame; skipped when !check).
+// ev (or null): two events recorded after stage 6 and after stage 7.
+hipError_t launch_zs_write(const uint8_t *zst, zs::Frame *frames, const zs::Block *blocks, uint32_t nb, uint64_t n,
+                           const uint32_t *lit_base, const uint32_t *seq_base, const uint8_t *lit, const zs::SeqRec *seq,
+                           const uint32_t *ooff, uint8_t *out, bool check, int32_t *status, uint32_t *bad,
+                           hipStream_t st, hipEvent_t *ev = nullptr);
 
 // Pipelined segments: the arena's chunks are cut into K host-known ranges
 // [cb[k], cb[k+1]); record range k is [rb[k], rb[k+1]) -- the records whose ids

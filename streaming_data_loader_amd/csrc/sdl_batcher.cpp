@@ -227,6 +227,8 @@ const char *kStageNames[] = {"chunk_ranges", "tokenize", "scan_chunks", "compact
 constexpr int kStages = 7;
 // pipelined segments: the tokenize launches, then the downstream work left after the last one
 const char *kPipedStageNames[] = {"chunk_ranges", "tokenize", "downstream_tail"};
+// sdl_zstd_inflate_device (its host syncs fall into the stage before them)
+const char *kZstdStageNames[] = {"zs_index", "zs_parse_link", "zs_decode", "zs_chain", "zs_literals", "zs_matches", "zs_checksum"};
 // segments per call (SDL_SEGMENTS) and the fewest 1 KiB chunks a pipelined
 // segment holds (SDL_SEG_MIN_CHUNKS, default 16 MiB of text); read when a
 // handle is created
@@ -315,6 +317,15 @@ struct sdl_batcher {
     DevBuf<int32_t> z_status;
     DevBuf<unsigned long long> z_total;
     DevBuf<uint8_t> z_out;
+    // zstd frame decode provider step (sdl_zstd_inflate_device): frame and block records, the scans'
+    // inputs and outputs, the literal arena and the sequence records (outputs reuse z_out / z_off /
+    // z_status / z_bad)
+    DevBuf<zs::Frame> zs_frames;
+    DevBuf<zs::Block> zs_blocks;
+    DevBuf<uint32_t> zs_nblk, zs_first, zs_lit_tot, zs_seq_tot, zs_lit_base, zs_seq_base;
+    DevBuf<unsigned long long> zs_totals;
+    DevBuf<uint8_t> zs_lit;
+    DevBuf<zs::SeqRec> zs_seq;
     // ... large members in chunks (inflate_chunked)
     DevBuf<uint64_t> zc_nominal, zc_found, zc_start, zc_hdr, zc_end, zc_endhdr, zc_pos;
     DevBuf<uint32_t> zc_list, zc_tgt, zc_next, zc_len, zc_flags, zc_order, zc_crc, zc_shift, zc_stats;
@@ -1950,6 +1961,158 @@ int sdl_gzip_split_members(const uint8_t *gz, uint64_t len, uint64_t *offsets, u
     }
     *n_members = off.size() - 1;
     if (!offsets || cap < off.size()) return fail(SDL_ERR_CAPACITY, "offsets needs n_members + 1 entries");
+    std::memcpy(offsets, off.data(), off.size() * sizeof(uint64_t));
+    return SDL_OK;
+}
+
+namespace {
+const char *zs_reason(int32_t s) {
+    static const char *const names[] = {"ok",
+                                        "frame range outside the buffer, or not exactly one frame",
+                                        "input ends inside the frame",
+                                        "not a zstd frame (magic or a reserved header bit)",
+                                        "the frame names a dictionary (Dictionary_ID)",
+                                        "window log or offset code beyond the supported limit",
+                                        "block type 3",
+                                        "block size over Block_Maximum_Size",
+                                        "bad literals section header",
+                                        "bad Huffman tree description",
+                                        "bad FSE table description",
+                                        "bad sequences section header",
+                                        "a bitstream did not end exactly",
+                                        "offset before the frame's start",
+                                        "decoded size differs from Frame_Content_Size",
+                                        "XXH64 content checksum mismatch",
+                                        "the decoder made no progress"};
+    return s >= 0 && s < (int32_t)(sizeof(names) / sizeof(names[0])) ? names[s] : "unknown";
+}
+}  // namespace
+
+int sdl_zstd_inflate_device(sdl_batcher *h, const uint8_t *d_zst, uint64_t zst_len, const uint64_t *d_frame_offsets,
+                            uint64_t n_frames, uint32_t flags, void *stream, sdl_inflated *out) {
+    if (!h || !out || (n_frames && (!d_zst || !d_frame_offsets))) return fail(SDL_ERR_ARG, "null argument");
+    if (flags & ~SDL_ZSTD_NO_CHECKSUM) return fail(SDL_ERR_ARG, "unknown flag bits");
+    if (zst_len >= (1ull << 32)) return fail(SDL_ERR_CAPACITY, "zstd buffer must be < 4 GiB per call");
+    if (n_frames >= (1ull << 31)) return fail(SDL_ERR_CAPACITY, "too many zstd frames in one call");
+    if (((uintptr_t)d_zst & 15u) != 0) return fail(SDL_ERR_ARG, "d_zst must be 16-byte aligned");
+    try {
+        hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+        const size_t n = (size_t)n_frames;
+        h->z_size.ensure(n + 1);
+        h->z_off.ensure(n + 1);
+        h->z_status.ensure(n + 1);
+        h->z_bad.ensure(2);
+        h->zs_frames.ensure(n + 1);
+        h->zs_nblk.ensure(n + 1);
+        h->zs_first.ensure(n + 1);
+        h->zs_lit_tot.ensure(n + 1);
+        h->zs_seq_tot.ensure(n + 1);
+        h->zs_lit_base.ensure(n + 1);
+        h->zs_seq_base.ensure(n + 1);
+        h->zs_totals.ensure(4);
+        h->scan_tmp.ensure((size_t)scan_tmp_words(std::max<int64_t>((int64_t)n, 1)) + 1);
+        unsigned long long totals[3] = {0, 0, 0};
+        uint32_t nb = 0;
+        h->n_stages = kStages;
+        h->stage_names = kZstdStageNames;
+        auto mark = [&](int i) {
+            if (h->profiling) HIP_TRY(hipEventRecord(h->ev[i], st));
+        };
+        mark(0);
+        if (n) {
+            HIP_TRY(hipMemsetAsync(h->zs_totals.p, 0, 4 * sizeof(unsigned long long), st));
+            // stage 1: count the blocks, scan, (sync: the block records are sized), fill
+            HIP_TRY(launch_zs_index(d_zst, zst_len, d_frame_offsets, n_frames, h->zs_frames.p, nullptr, nullptr,
+                                    h->zs_nblk.p, 0, st));
+            HIP_TRY(launch_exclusive_scan(h->zs_nblk.p, h->zs_first.p, (int64_t)n, h->scan_tmp.p, st));
+            HIP_TRY(hipMemcpyAsync(&nb, h->zs_first.p + n, sizeof(nb), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            // (a block is >= 3 bytes of a < 4 GiB input: the count cannot wrap)
+            h->zs_blocks.ensure((size_t)nb + 1);
+            HIP_TRY(launch_zs_index(d_zst, zst_len, d_frame_offsets, n_frames, h->zs_frames.p, h->zs_blocks.p,
+                                    h->zs_first.p, h->zs_nblk.p, nb, st));
+            mark(1);
+            // stages 2, 3; (sync: the literal arena and the sequence records are sized)
+            HIP_TRY(launch_zs_parse(d_zst, h->zs_frames.p, h->zs_blocks.p, nb, st));
+            HIP_TRY(launch_zs_link(h->zs_frames.p, h->zs_blocks.p, n_frames, h->zs_lit_tot.p, h->zs_seq_tot.p,
+                                   h->zs_totals.p, st));
+            HIP_TRY(hipMemcpyAsync(totals, h->zs_totals.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            // the headers' sizes are untrusted until decoded: they bound the arenas, never a kernel's writes
+            if (totals[0] >= (1ull << 32) - 64 || totals[1] >= (1ull << 28))
+                return fail(SDL_ERR_CAPACITY, "zstd frames hold >= 4 GiB of literals or sequence records in one call");
+            HIP_TRY(launch_exclusive_scan(h->zs_lit_tot.p, h->zs_lit_base.p, (int64_t)n, h->scan_tmp.p, st));
+            HIP_TRY(launch_exclusive_scan(h->zs_seq_tot.p, h->zs_seq_base.p, (int64_t)n, h->scan_tmp.p, st));
+            h->zs_lit.ensure((size_t)totals[0] + 16);
+            h->zs_seq.ensure((size_t)totals[1] + 1);
+            mark(2);
+            // stages 4, 5; (sync: the output is sized)
+            HIP_TRY(launch_zs_decode(d_zst, h->zs_frames.p, h->zs_blocks.p, nb, h->zs_lit_base.p, h->zs_seq_base.p,
+                                     h->zs_lit.p, h->zs_seq.p, st));
+            mark(3);
+            HIP_TRY(launch_zs_chain(h->zs_frames.p, h->zs_blocks.p, n_frames, h->z_size.p, h->zs_totals.p, st));
+            HIP_TRY(hipMemcpyAsync(totals + 2, h->zs_totals.p + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        const unsigned long long total = totals[2];
+        if (total >= (1ull << 32) - 64) return fail(SDL_ERR_CAPACITY, "zstd frames decode to >= 4 GiB in one call");
+        h->z_out.ensure((size_t)total + 48);
+        HIP_TRY(hipMemsetAsync(h->z_out.p + total, 0, 32, st));
+        uint32_t bad[2] = {0, 0xFFFFFFFFu};
+        if (n) {
+            HIP_TRY(launch_exclusive_scan(h->z_size.p, h->z_off.p, (int64_t)n, h->scan_tmp.p, st));
+            HIP_TRY(hipMemcpyAsync(h->z_bad.p, bad, sizeof(bad), hipMemcpyHostToDevice, st));
+            mark(4);
+            // stages 6, 7, 8
+            HIP_TRY(launch_zs_write(d_zst, h->zs_frames.p, h->zs_blocks.p, nb, n_frames, h->zs_lit_base.p,
+                                    h->zs_seq_base.p, h->zs_lit.p, h->zs_seq.p, h->z_off.p, h->z_out.p,
+                                    !(flags & SDL_ZSTD_NO_CHECKSUM), h->z_status.p, h->z_bad.p, st,
+                                    h->profiling ? h->ev + 5 : nullptr));
+            mark(7);
+            HIP_TRY(hipMemcpyAsync(bad, h->z_bad.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        } else {
+            for (int i = 1; i <= kStages; ++i) mark(i);
+            HIP_TRY(hipMemsetAsync(h->z_off.p, 0, sizeof(uint32_t), st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        std::memset(out, 0, sizeof(*out));
+        out->d_out = h->z_out.p;
+        out->d_member_out = h->z_off.p;
+        out->d_status = h->z_status.p;
+        out->out_bytes = total;
+        out->n_members = n_frames;
+        out->n_bad = bad[0];
+        if (bad[0]) {
+            int32_t s = 0;
+            HIP_TRY(hipMemcpy(&s, h->z_status.p + bad[1], sizeof(s), hipMemcpyDeviceToHost));
+            return fail(SDL_ERR_DATA, "zstd frame " + std::to_string(bad[1]) + ": " + zs_reason(s) + " (" +
+                                          std::to_string(bad[0]) + " of " + std::to_string(n_frames) + " frames failed)");
+        }
+        return SDL_OK;
+    } catch (HipError &e) {
+        return fail(SDL_ERR_HIP, e.what());
+    } catch (std::exception &e) {
+        return fail(SDL_ERR_ARG, e.what());
+    }
+}
+
+int sdl_zstd_split_frames(const uint8_t *zst, uint64_t len, uint64_t *offsets, uint64_t cap, uint64_t *n_frames) {
+    if ((!zst && len) || !n_frames) return fail(SDL_ERR_ARG, "null argument");
+    std::vector<uint64_t> off{0};
+    while (off.back() < len) {
+        zs::FrameInfo fi;
+        uint64_t bytes = 0;
+        uint32_t nb = 0;
+        const int32_t st = zs::frame_extent(zst + off.back(), len - off.back(), fi, bytes, nb);
+        if (st) {
+            *n_frames = off.size() - 1;
+            return fail(SDL_ERR_DATA, "no zstd frame at byte " + std::to_string(off.back()) + ": " + zs_reason(st));
+        }
+        off.push_back(off.back() + bytes);
+    }
+    *n_frames = off.size() - 1;
+    if (!offsets || cap < off.size()) return fail(SDL_ERR_CAPACITY, "offsets needs n_frames + 1 entries");
     std::memcpy(offsets, off.data(), off.size() * sizeof(uint64_t));
     return SDL_OK;
 }

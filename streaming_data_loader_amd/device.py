@@ -233,6 +233,20 @@ class DeviceBatcher:
             return out
         return rc, out
 
+    def zstd_inflate(self, zst_ptr, zst_len, frame_offsets_ptr, n_frames, flags=0, stream=0, check=True):
+        """The provider's zstd decode on the device (sdl_zstd_inflate_device): Zstandard frames in a
+        16-B aligned device buffer -> their bytes back to back in a device arena owned by this
+        handle (native.Inflated, frames in the place of members).  check=False returns
+        (rc, Inflated) instead of raising on corrupt frames."""
+        out = native.Inflated()
+        rc = native.load().sdl_zstd_inflate_device(self._h, ctypes.c_void_p(zst_ptr), zst_len,
+                                                   ctypes.c_void_p(frame_offsets_ptr), n_frames, flags,
+                                                   ctypes.c_void_p(stream or None), ctypes.byref(out))
+        if check:
+            native.check(rc)
+            return out
+        return rc, out
+
     def pickle_frames(self, result, n_rows=None, flush_partial=True, stream=0):
         """Transport step on the device: the batches of `result` (the last
         process*() call) as serde_pickle frames (DeviceFrames)."""

@@ -25,6 +25,7 @@ EXPORTS = [
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
     "sdl_gzip_inflate_device", "sdl_gzip_inflate_first_device", "sdl_gzip_split_members", "sdl_build_id",
+    "sdl_zstd_inflate_device", "sdl_zstd_split_frames",
     "sdl_shard_records", "sdl_multi_create", "sdl_multi_destroy", "sdl_multi_push_many", "sdl_multi_handle",
 ]
 
@@ -100,6 +101,10 @@ class Inflated(ctypes.Structure):
 GZ_OK, GZ_E_RANGE, GZ_E_TRUNC, GZ_E_HEADER, GZ_E_HCRC, GZ_E_BTYPE, GZ_E_STORED, GZ_E_CODES, GZ_E_CODE, \
     GZ_E_FAR, GZ_E_OVER, GZ_E_SIZE, GZ_E_TRAIL, GZ_E_CRC, GZ_E_STALL = range(15)
 SDL_ERR_DATA = -8
+# per-frame status codes of sdl_zstd_inflate_device (csrc/kernels.hpp ZS_*)
+ZS_OK, ZS_E_RANGE, ZS_E_TRUNC, ZS_E_MAGIC, ZS_E_DICT, ZS_E_WINDOW, ZS_E_BTYPE, ZS_E_BSIZE, ZS_E_LITHDR, ZS_E_HUF, \
+    ZS_E_FSE, ZS_E_SEQHDR, ZS_E_ENDBITS, ZS_E_FAR, ZS_E_SIZE, ZS_E_CHECKSUM, ZS_E_STALL = range(17)
+SDL_ZSTD_NO_CHECKSUM = 1
 
 
 FRAME_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64)
@@ -184,6 +189,10 @@ def load(path=LIB_PATH):
     L.sdl_gzip_inflate_first_device.restype = i64
     L.sdl_gzip_split_members.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64)]
     L.sdl_gzip_split_members.restype = i64
+    L.sdl_zstd_inflate_device.argtypes = [vp, vp, u64, vp, u64, ctypes.c_uint32, vp, ctypes.POINTER(Inflated)]
+    L.sdl_zstd_inflate_device.restype = i64
+    L.sdl_zstd_split_frames.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64)]
+    L.sdl_zstd_split_frames.restype = i64
     L.sdl_shard_records.argtypes = [vp, u64, ctypes.c_uint32, vp]
     L.sdl_shard_records.restype = i64
     L.sdl_multi_create.argtypes = [ctypes.POINTER(Config), ctypes.c_char_p, ctypes.c_char_p, vp, ctypes.c_uint32,
@@ -256,6 +265,21 @@ def gzip_split_members(buf):
         check(rc)
     off = np.zeros(n.value + 1, dtype=np.uint64)
     check(L.sdl_gzip_split_members(b, len(b), off.ctypes.data, off.size, ctypes.byref(n)))
+    return off
+
+
+def zstd_split_frames(buf):
+    """sdl_zstd_split_frames (host only): frame offsets (numpy u64 [n + 1]) of one .zst file,
+    skippable frames included; raises SDLError (SDL_ERR_DATA) on bytes that are no frame."""
+    import numpy as np
+    L = load()
+    b = bytes(buf)
+    n = ctypes.c_uint64(0)
+    rc = L.sdl_zstd_split_frames(b, len(b), None, 0, ctypes.byref(n))
+    if rc < 0 and rc != -7:
+        check(rc)
+    off = np.zeros(n.value + 1, dtype=np.uint64)
+    check(L.sdl_zstd_split_frames(b, len(b), off.ctypes.data, off.size, ctypes.byref(n)))
     return off
 
 
