@@ -120,8 +120,11 @@ constexpr int UNI_JP_OFF = STAGE + STAGE / 2;         // job payloads: uint4 [UN
 constexpr int UNI_JM_OFF = UNI_JP_OFF + 4 * UNI_VPC;  // job metas: L | pos << 6 | entry << 18
 constexpr int UNI_JN_OFF = UNI_JM_OFF + UNI_VPC;      // the chunk's job count
 constexpr uint32_t UNI_JOB_BIT = 0x40000000u;
-static_assert(UNI_JN_OFF < UNI_STAGE && (UNI_JP_OFF * 4) % 16 == 0 && (UNI_STAGE * 4) % 16 == 0,
+static_assert(UNI_JN_OFF + 2 <= UNI_STAGE && (UNI_JP_OFF * 4) % 16 == 0 && (UNI_STAGE * 4) % 16 == 0,
               "the Viterbi jobs fit the tokc slice behind its list");
+// the chunk kernel's one scan packs entries | jobs << 11 | payload units << 19: a chunk has at most
+// STAGE entries (every piece's entries fit its stage room), UNI_VPC jobs and 4 units a job
+static_assert(STAGE <= 0x7FF && UNI_VPC <= 0xFF && 4 * UNI_VPC <= 0x1FFF, "the packed scan's fields hold a chunk's counts");
 constexpr int UNI_LANE_NORM = 256;  // normalized bytes per lane of the long-item kernel
 constexpr int UNI_HUGE_NORM = 1 << 18;  // ... per wave of the huge-item kernel
 // grapheme / whitespace properties (tools/make_t5_tables.py)
