@@ -386,7 +386,9 @@ typedef struct sdl_tokenizer_info {
     int32_t eos_id;             /* </s> / <|endoftext|> (TokenizerInfo.eos), -1 if none */
     int32_t max_piece_bytes;
     uint64_t word_table_entries; /* device word-table / hash entries */
-    int32_t reserved[6];
+    int32_t normalizer_flags;   /* WordPiece BertNormalizer: bit 0 keeps case (lowercase=false),
+                                 * bit 1 keeps accents (strip_accents=false); 0 otherwise */
+    int32_t reserved[5];
 } sdl_tokenizer_info;
 int sdl_tokenizer_info_get(const char *tokenizer_path, const char *data_dir, sdl_tokenizer_info *out);
 

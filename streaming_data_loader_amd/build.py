@@ -69,12 +69,77 @@ def embedded_id(lib):
     return data[i + len(BUILD_ID_MARK):i + len(BUILD_ID_MARK) + 64].decode("ascii", "replace") if i >= 0 else None
 
 
+# The BertNormalizer settings beside bert-base-uncased's (cased, accent-keeping): their Unicode
+# tables and the cased proxy vocabulary are committed once, under tests/golden/bert_normalizer/
+# -- the one place of this repository that takes new binary files -- by
+# tools/make_unicode_tables.py and tools/make_proxy_cased_assets.py, and the build installs
+# them next to the library.  A tree without that directory builds as before and serves every
+# tokenizer but those settings' (the loader names the missing table).
+SETTINGS_SRC = os.path.join(REPO, "tests", "golden", "bert_normalizer")
+SETTINGS_TABLES = ["bert_cased_unicode.bin", "bert_uncased_accents_unicode.bin", "bert_cased_stripped_unicode.bin"]
+CASED_PROXY = os.path.join(PKG, "assets", "bert_cased_proxy")
+CASED_VOCAB_GZ = os.path.join(SETTINGS_SRC, "bert_cased_proxy_vocab.txt.gz")
+
+
+def cased_tokenizer_json(vocab):
+    """What tokenizers' BertWordPieceTokenizer(vocab.txt, lowercase=False, strip_accents=False)
+    saves: bert-base-cased's tokenizer.json layout around the vocabulary."""
+    def added(i):
+        return {"id": i, "content": vocab[i], "single_word": False, "lstrip": False, "rstrip": False,
+                "normalized": False, "special": True}
+    ids = {p: i for i, p in enumerate(vocab)}
+    return {"version": "1.0", "truncation": None, "padding": None,
+            "added_tokens": [added(ids[t]) for t in ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]")],
+            "normalizer": {"type": "BertNormalizer", "clean_text": True, "handle_chinese_chars": True,
+                           "strip_accents": False, "lowercase": False},
+            "pre_tokenizer": {"type": "BertPreTokenizer"},
+            "post_processor": {"type": "BertProcessing", "sep": ["[SEP]", ids["[SEP]"]], "cls": ["[CLS]", ids["[CLS]"]]},
+            "decoder": {"type": "WordPiece", "prefix": "##", "cleanup": True},
+            "model": {"type": "WordPiece", "unk_token": "[UNK]", "continuing_subword_prefix": "##",
+                      "max_input_chars_per_word": 100, "vocab": ids}}
+
+
+def install_assets():
+    """Puts the tables of the other BertNormalizer settings into data/ and the cased proxy
+    tokenizer (vocab.txt, tokenizer.json) into assets/bert_cased_proxy/ (git-ignored, like the
+    library); files that are there with the right content are left alone."""
+    import gzip
+    import json
+
+    if not os.path.isdir(SETTINGS_SRC):
+        return
+
+    def put(path, data):
+        try:
+            with open(path, "rb") as f:
+                if f.read() == data:
+                    return
+        except OSError:
+            pass
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        tmp = f"{path}.tmp{os.getpid()}"
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, path)  # (several test processes may install at once)
+
+    for name in SETTINGS_TABLES:
+        with open(os.path.join(SETTINGS_SRC, name), "rb") as f:
+            put(os.path.join(PKG, "data", name), f.read())
+    with gzip.open(CASED_VOCAB_GZ, "rb") as f:
+        text = f.read()
+    put(os.path.join(CASED_PROXY, "vocab.txt"), text)
+    vocab = text.decode("utf-8").split("\n")[:-1]
+    put(os.path.join(CASED_PROXY, "tokenizer.json"),
+        json.dumps(cased_tokenizer_json(vocab), ensure_ascii=False, indent=2).encode("utf-8"))
+
+
 def build(verbose=False, force=False, jobs=4, defines=(), lib=None, build_dir=None):
     """defines: extra -D macros (diagnostic builds go to their own lib/build_dir).
 
     A library whose embedded build id equals source_hash() is used as is (the
     GPU box gets the library but not the objects: nothing is recompiled
     there); otherwise the changed objects are rebuilt and the id relinked."""
+    install_assets()
     lib = lib or LIB
     bdir = build_dir or BUILD
     os.makedirs(bdir, exist_ok=True)

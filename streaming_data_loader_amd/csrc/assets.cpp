@@ -43,7 +43,14 @@ static std::string read_file(const std::string &path) {
 }
 
 static void load_unicode(const std::string &path, HostTokenizer &t) {
-    std::string d = read_file(path);
+    std::string d;
+    try {
+        d = read_file(path);
+    } catch (std::runtime_error &e) {
+        // (the tables beside bert_uncased_unicode.bin are put into data/ by the build)
+        throw std::runtime_error(std::string(e.what()) + ": the Unicode table of this BertNormalizer setting "
+                                 "(python -m streaming_data_loader_amd.build installs it)");
+    }
     if (d.size() < 20 || std::memcmp(d.data(), "SDLU", 4) != 0) throw std::runtime_error("bad unicode table " + path);
     uint32_t hdr[4];
     std::memcpy(hdr, d.data() + 4, 16);
@@ -57,28 +64,36 @@ static void load_unicode(const std::string &path, HostTokenizer &t) {
     std::memcpy(t.upage.data(), d.data() + 20, 2 * np);
     std::memcpy(t.uentry.data(), d.data() + 20 + 2 * np, 4 * 128 * nb);
     std::memcpy(t.upool.data(), d.data() + 20 + 2 * np + 4 * 128 * nb, pb);
-    // The kernels' ASCII fast path lower-cases A-Z itself: check the table agrees.
+    // The kernels' ASCII fast path lower-cases A-Z itself, or with a cased table leaves every
+    // byte as it is: check the table agrees.
     for (uint32_t c = 0; c < 128; ++c) {
         uint32_t e = t.uentry[(size_t)t.upage[0] * 128 + c];
         if ((e & 3u) != UC_OTHER) continue;
-        uint8_t want = (uint8_t)((c - 'A' < 26u) ? c + 32 : c);
+        uint8_t want = (uint8_t)((!t.cased && c - 'A' < 26u) ? c + 32 : c);
         uint8_t got = (e & 4u) ? (uint8_t)c : t.upool[(e >> 8) + 2];
         if (got != want || (!(e & 4u) && t.upool[e >> 8] != 1))
             throw std::runtime_error("unicode table: unexpected ASCII mapping");
     }
 }
 
-static bool is_bert_normalizer(const JValue *n) {
-    if (!n) return false;
-    const JValue *t = n->get("type");
-    if (!t || !t->is_str("BertNormalizer")) return false;
+// The BertNormalizer settings the WordPiece path takes: any lowercase / strip_accents (null:
+// follow lowercase), each with a Unicode table of its own; clean_text and
+// handle_chinese_chars must be true.  Throws on anything else.
+struct BertSettings {
+    bool lowercase, strip_accents;
+};
+static BertSettings bert_normalizer_settings(const JValue *n) {
+    const JValue *t = n ? n->get("type") : nullptr;
+    if (!t || !t->is_str("BertNormalizer")) throw std::runtime_error("normalizer must be BertNormalizer");
     auto flag = [&](const char *k, bool dflt) {
         const JValue *v = n->get(k);
         return (v && v->kind == JValue::BOOL) ? v->b : dflt;
     };
-    const JValue *sa = n->get("strip_accents");
-    bool strip = (sa && sa->kind == JValue::BOOL) ? sa->b : flag("lowercase", true);
-    return flag("clean_text", true) && flag("handle_chinese_chars", true) && flag("lowercase", true) && strip;
+    if (!flag("clean_text", true)) throw std::runtime_error("BertNormalizer: clean_text=false is not supported");
+    if (!flag("handle_chinese_chars", true))
+        throw std::runtime_error("BertNormalizer: handle_chinese_chars=false is not supported");
+    const bool lower = flag("lowercase", true);
+    return BertSettings{lower, flag("strip_accents", lower)};
 }
 
 static int find_piece(const HostTokenizer &t, const std::string &s) {
@@ -1010,8 +1025,9 @@ void load_tokenizer(const std::string &path, const std::string &data_dir, HostTo
         const JValue *mx = model->get("max_input_chars_per_word");
         if (mx && mx->kind == JValue::NUM && (int)mx->num != MAX_WORD_CHARS)
             throw std::runtime_error("max_input_chars_per_word must be 100");
-        if (!is_bert_normalizer(root.get("normalizer")))
-            throw std::runtime_error("normalizer must be BertNormalizer(lowercase, strip accents, clean_text, chinese)");
+        const BertSettings bs = bert_normalizer_settings(root.get("normalizer"));
+        t.cased = !bs.lowercase;
+        t.keeps_accents = !bs.strip_accents;
         const JValue *pre = root.get("pre_tokenizer");
         if (!pre || !pre->get("type") || !pre->get("type")->is_str("BertPreTokenizer"))
             throw std::runtime_error("pre_tokenizer must be BertPreTokenizer");
@@ -1096,7 +1112,9 @@ void load_tokenizer(const std::string &path, const std::string &data_dir, HostTo
         throw std::runtime_error("tokenizer lacks [UNK]/[CLS]/[SEP]");
     set_added(t);
     build_vocab_table(t);
-    load_unicode(data_dir + "/bert_uncased_unicode.bin", t);
+    load_unicode(data_dir + (t.cased ? (t.keeps_accents ? "/bert_cased_unicode.bin" : "/bert_cased_stripped_unicode.bin")
+                                     : (t.keeps_accents ? "/bert_uncased_accents_unicode.bin" : "/bert_uncased_unicode.bin")),
+                 t);
     check_ascii_and_ids(t);
     to_device_entries(t);
     wp_iso_ids(t);

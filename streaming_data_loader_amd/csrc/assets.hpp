@@ -20,7 +20,10 @@ struct HostTokenizer {
     int cls_id = -1, sep_id = -1, pad_id = -1, mask_id = -1;  // TokenizerInfo (tokenizer_wrapper.rs:45-92)
     int tpl_cls = -1, tpl_sep = -1;                    // TemplateProcessing "[CLS] $A [SEP]" ids
 
-    // ---- Unicode tables (data/bert_uncased_unicode.bin) ----------------------
+    // ---- BertNormalizer setting and its Unicode table (data/bert_*_unicode.bin: uncased,
+    //      uncased_accents, cased, cased_stripped) ----------------------------------
+    bool cased = false;          // lowercase=false: the chunk kernel's CASED instantiation
+    bool keeps_accents = false;  // strip_accents=false
     std::vector<uint16_t> upage;
     std::vector<uint32_t> uentry;
     std::vector<uint8_t> upool;
@@ -80,9 +83,10 @@ std::vector<int> unigram_encode_word(const HostTokenizer &t, const uint8_t *w, s
 std::vector<int> bpe_encode_bytes(const HostTokenizer &t, const uint8_t *s, size_t n);
 
 // Loads a HF tokenizer.json (WordPiece model with BertNormalizer +
-// BertPreTokenizer, as bert-base-uncased) or a WordPiece vocab.txt, plus the
-// Unicode table from data_dir.  Throws std::runtime_error with a message on
-// anything unsupported.
+// BertPreTokenizer, as bert-base-uncased or bert-base-cased) or a WordPiece
+// vocab.txt (uncased), plus the Unicode table of the normalizer's setting
+// from data_dir.  Throws std::runtime_error with a message on anything
+// unsupported.
 void load_tokenizer(const std::string &path, const std::string &data_dir, HostTokenizer &out);
 
 // Slot hash of a vocab piece (payload bytes, cont = "##"-prefixed); the

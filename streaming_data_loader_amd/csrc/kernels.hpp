@@ -18,8 +18,10 @@ hipError_t launch_chunk_ranges(const uint64_t *off, int64_t R, int64_t N, uint32
 
 // tokenize_wordpiece.hip: text arena -> per-chunk token lists (packed u16, STAGE
 // slots a chunk) + boundary offsets (after launch_chunk_ranges), for chunks
-// [c_begin, c_end) (c_end < 0: all).
-hipError_t launch_wordpiece_chunks(const DevTok &T, const DevFirst &F, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
+// [c_begin, c_end) (c_end < 0: all).  cased: the tokenizer's BertNormalizer keeps case
+// (HostTokenizer::cased) -- the kernel's CASED instantiation, which leaves ASCII letters alone.
+hipError_t launch_wordpiece_chunks(const DevTok &T, const DevFirst &F, bool cased, const uint8_t *text, int64_t N,
+                                   const uint64_t *off, int64_t R,
                                    uint32_t *ranges, uint16_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
                                    hipStream_t st, int64_t c_begin = 0, int64_t c_end = -1);
 

@@ -697,14 +697,14 @@ struct sdl_batcher {
                                       rec_local.p, long_count.p, long_list.p, cap, long_scratch.p, bpe_err.p, st));
             downstream(0, st);
         } else if (!piped) {
-            HIP_TRY(launch_wordpiece_chunks(dt, dfirst, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st, 0,
-                                            -1));
+            HIP_TRY(launch_wordpiece_chunks(dt, dfirst, tok.cased, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p,
+                                            rec_local.p, st, 0, -1));
             downstream(0, st);
         } else {
             ensure_pipe_events(sc.K);
             for (int k = 0; k < sc.K; ++k) {
-                HIP_TRY(launch_wordpiece_chunks(dt, dfirst, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p, rec_local.p, st,
-                                                sc.cb[k], sc.cb[k + 1]));
+                HIP_TRY(launch_wordpiece_chunks(dt, dfirst, tok.cased, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p,
+                                                rec_local.p, st, sc.cb[k], sc.cb[k + 1]));
                 HIP_TRY(hipEventRecord(pipe_ev[k], st));
                 HIP_TRY(hipStreamWaitEvent(stream2, pipe_ev[k], 0));
                 downstream(k, stream2);
@@ -2514,6 +2514,7 @@ int sdl_tokenizer_info_get(const char *tokenizer_path, const char *data_dir, sdl
         for (auto &p : t.pieces) mx = std::max(mx, (int)p.size());
         out->max_piece_bytes = mx;
         out->word_table_entries = t.kind == TOK_WORDPIECE ? 0 : t.word_table_entries;
+        out->normalizer_flags = (t.cased ? 1 : 0) | (t.keeps_accents ? 2 : 0);
         return SDL_OK;
     } catch (std::exception &e) {
         return fail(SDL_ERR_IO, e.what());

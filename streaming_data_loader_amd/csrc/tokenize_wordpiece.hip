@@ -4,7 +4,9 @@
 // record at a time in TokenizerHolder::get_ids -> tokenizers::Tokenizer::encode
 // (rust/src/tokenizer/tokenizer_holder.rs:19-28; crate tokenizers 0.13.1):
 //   AddedVocabulary split (raw-text match of the added tokens)
-//   -> BertNormalizer (clean_text, CJK padding, NFD + strip Mn, lowercase)
+//   -> BertNormalizer (clean_text, CJK padding; NFD + strip Mn and lowercase as the
+//      tokenizer sets them: the Unicode table carries the setting, and the kernel's
+//      CASED instantiation leaves ASCII letters as they are)
 //   -> BertPreTokenizer (split on whitespace, isolate punctuation)
 //   -> WordPiece (greedy longest-match-first, "##" continuation, 100-char cap).
 // The template's [CLS]/[SEP] and the wrapper's framing are added at row
@@ -249,8 +251,9 @@ __device__ __forceinline__ int64_t word_extent(const Ctx &C, int64_t p, int64_t 
 // Normalized bytes of the word [p, i) into buf (private or LDS); returns the
 // count.  NFD canonical ordering of the kept combining marks: a run of them is
 // appended as it comes and sorted in place (stable, by ccc) when a starter --
-// kept, removed or inside a precomposed char -- ends it.
-template <typename Buf>
+// kept, removed or inside a precomposed char -- ends it.  CASED: the normalizer keeps
+// case, so an ASCII letter goes in as it is (every other char's form is the table's).
+template <bool CASED, typename Buf>
 __device__ __forceinline__ int word_materialize(const Ctx &C, int64_t p, int64_t i, Buf *buf) {
     const DevTok &T = *C.T;
     int nb = 0;
@@ -291,7 +294,7 @@ __device__ __forceinline__ int word_materialize(const Ctx &C, int64_t p, int64_t
         if (b < 0x80u) {
             if (ascii_vclass(b) == V_OTHER) {
                 flush();
-                buf[nb++] = (uint8_t)((b - 'A' < 26u) ? b + 32u : b);
+                buf[nb++] = (uint8_t)((!CASED && b - 'A' < 26u) ? b + 32u : b);
             }
             ++q;
             continue;
@@ -342,8 +345,9 @@ __device__ __forceinline__ int word_materialize(const Ctx &C, int64_t p, int64_t
 // General WORD piece [p, i) of at most MAX_WORD_CHARS normalized chars, materialized in
 // `buf` (LDS, MAX_WORD_BYTES), WordPiece one probe at a time (words whose normalization
 // exceeds the lattice's LW_MAX bytes).
+template <bool CASED>
 __device__ __forceinline__ int word_general(const Ctx &C, int64_t p, int64_t i, lds_u8 *buf, lds_u16 *out) {
-    const int nb = word_materialize(C, p, i, buf);
+    const int nb = word_materialize<CASED>(C, p, i, buf);
     return wordpiece_general(*C.T, buf, nb, out);
 }
 
@@ -368,6 +372,7 @@ __device__ __forceinline__ int w16_prev_char(const W16 &w, int end, int start) {
 // BertNormalizer output of the WORD piece at p (or of the single ISO char at
 // p if iso) into registers.  Returns false if the normalized word does not fit
 // in 16 bytes (then the scratch path handles it, including the 100-char rule).
+template <bool CASED>
 __device__ __forceinline__ bool normalize_w16(const Ctx &C, int64_t p, int64_t rec_end, bool iso, W16 &w, int &L) {
     const DevTok &T = *C.T;
     w = W16{0, 0, 0, 0};
@@ -380,7 +385,7 @@ __device__ __forceinline__ bool normalize_w16(const Ctx &C, int64_t p, int64_t r
             if (iso || c == V_OTHER) {
                 if (!iso && T.n_special && b == T.opener && special_match(C, i) >= 0) break;
                 if (nb >= 16) return false;
-                w16_put(w, nb++, (b - 'A' < 26u) ? b + 32u : b);
+                w16_put(w, nb++, (!CASED && b - 'A' < 26u) ? b + 32u : b);
                 ++i;
                 if (iso) break;
                 continue;
@@ -463,6 +468,11 @@ constexpr int WP_WAVES = 5;
 // fixture 1.14 -> 1.19 ms, held-out 2.32 -> 2.40; 3: within noise) -- the
 // machine is bound by its lanes' probe latency, not by its step count.
 constexpr int WP_NPROBE = 2;
+// CASED: the tokenizer's BertNormalizer keeps case (lowercase=false).  A compile-time variant,
+// not a field of DevTok or DevFirst (their layout is shared with the BPE and Unigram kernels):
+// the uncased instantiation is the kernel as it was, and the cased one drops the lower-casing
+// of ASCII letters at its three sites -- word_setup, normalize_w16, word_materialize.
+template <bool CASED>
 __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_WAVES, 8))) void k_wordpiece_chunks(
     DevTok T, DevFirst F, const uint8_t *__restrict__ text, int64_t N, const uint64_t *__restrict__ off, int64_t R,
     const uint32_t *__restrict__ ranges, uint16_t *__restrict__ tokc, uint32_t *__restrict__ chunk_cnt,
@@ -815,8 +825,8 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     const lds_u32 *w32 = (const lds_u32 *)s_win;
     // word setup shared by (a) and (b): the word's length and fast flag from the two bitmaps
     // (both windows come with one read, next to the window's five dwords), its bytes
-    // lower-cased by one OR -- inside the length every byte is an ASCII letter or digit;
-    // returns false if the general path is needed
+    // lower-cased by one OR -- inside the length every byte is an ASCII letter or digit --
+    // or, CASED, as they are; returns false if the general path is needed
     auto word_setup = [&](int prel, W16 &lw, int &Lout) -> bool {
         const int wr = prel + HALO_L;
         const int a = wr >> 2;
@@ -828,7 +838,8 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                       __builtin_amdgcn_alignbyte(x3, x2, sh), __builtin_amdgcn_alignbyte(x4, x3, sh)};
         const WxExtent ex = wx_extent(wx_window((uint32_t)e0, (uint32_t)e1, q),
                                       wx_window((uint32_t)(e0 >> 32), (uint32_t)(e1 >> 32), q), raw.x);
-        const WxMask m = wx_lower_keep(raw.x, raw.y, raw.z, raw.w, ex.len);
+        const WxMask m = CASED ? wx_keep(raw.x, raw.y, raw.z, raw.w, ex.len)
+                               : wx_lower_keep(raw.x, raw.y, raw.z, raw.w, ex.len);
         lw = W16{m.x, m.y, m.z, m.w};
         Lout = ex.len;
         return ex.fast;
@@ -941,7 +952,7 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                         if (kind == V_OTHER && word_setup(prel, w, L)) {
                             fits = true;
                         } else {
-                            fits = normalize_w16(C, p, rec_end_of(C, rb_next, p),
+                            fits = normalize_w16<CASED>(C, p, rec_end_of(C, rb_next, p),
                                                  kind == V_ISO, w, L);
                         }
                         if (fits) {
@@ -1078,9 +1089,9 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
                     if (nch > MAX_WORD_CHARS) {
                         dout[0] = (uint16_t)T.unk_id;
                     } else if (nby > LW_MAX || T.wp_long_pieces) {
-                        stage_count(dprel, word_general(C, dp, iend, wb, dout));
+                        stage_count(dprel, word_general<CASED>(C, dp, iend, wb, dout));
                     } else {
-                        dL = word_materialize(C, dp, iend, wb);
+                        dL = word_materialize<CASED>(C, dp, iend, wb);
                         for (int k = dL; k < dL + 20; ++k) wb[k] = 0;
                     }
                 }
@@ -1246,15 +1257,20 @@ void print_phase_cycles() {
 }
 #endif
 
-hipError_t launch_wordpiece_chunks(const DevTok &T, const DevFirst &F, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
-                                   uint32_t *ranges, uint16_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
+hipError_t launch_wordpiece_chunks(const DevTok &T, const DevFirst &F, bool cased, const uint8_t *text, int64_t N,
+                                   const uint64_t *off, int64_t R, uint32_t *ranges, uint16_t *tokc, uint32_t *chunk_cnt, uint32_t *rec_local,
                                    hipStream_t st, int64_t c_begin, int64_t c_end) {
     const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
     if (c_end < 0 || c_end > n_chunks) c_end = n_chunks;
     if (c_begin < 0) c_begin = 0;
     if (c_end <= c_begin) return hipSuccess;
-    hipLaunchKernelGGL(k_wordpiece_chunks, dim3((unsigned)(c_end - c_begin)), dim3(TOK_THREADS), 0, st, T, F, text, N,
-                       off, R, ranges, tokc, chunk_cnt, rec_local, c_begin);
+    const dim3 grid((unsigned)(c_end - c_begin)), block(TOK_THREADS);
+    if (cased)
+        hipLaunchKernelGGL(k_wordpiece_chunks<true>, grid, block, 0, st, T, F, text, N, off, R, ranges, tokc, chunk_cnt,
+                           rec_local, c_begin);
+    else
+        hipLaunchKernelGGL(k_wordpiece_chunks<false>, grid, block, 0, st, T, F, text, N, off, R, ranges, tokc, chunk_cnt,
+                           rec_local, c_begin);
     return hipGetLastError();
 }
 

@@ -129,5 +129,11 @@ WP_EXTENT_FN WxMask wx_lower_keep(uint32_t x, uint32_t y, uint32_t z, uint32_t w
     return WxMask{(x | 0x20202020u) & m.x, (y | 0x20202020u) & m.y, (z | 0x20202020u) & m.z,
                   (w | 0x20202020u) & m.w};
 }
+// The first n bytes as they are, zero behind them: the word's form under a normalizer that
+// keeps case.
+WP_EXTENT_FN WxMask wx_keep(uint32_t x, uint32_t y, uint32_t z, uint32_t w, int n) {
+    const WxMask m = wx_keep_mask(n);
+    return WxMask{x & m.x, y & m.y, z & m.z, w & m.w};
+}
 
 }  // namespace sdl

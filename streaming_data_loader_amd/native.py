@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SDL_LIB") or os.path.join(PKG, "libsdl_batcher.so")
 DATA_DIR = os.path.join(PKG, "data")
 ASSETS = os.path.join(PKG, "assets")
 BERT_PROXY_TOKENIZER = os.path.join(ASSETS, "bert_proxy", "tokenizer.json")
+BERT_CASED_PROXY_TOKENIZER = os.path.join(ASSETS, "bert_cased_proxy", "tokenizer.json")  # (build.install_assets)
 GPT2_PROXY_TOKENIZER = os.path.join(ASSETS, "gpt2_proxy", "tokenizer.json")
 T5_PROXY_TOKENIZER = os.path.join(ASSETS, "t5_proxy", "tokenizer.json")
 
@@ -114,7 +115,9 @@ class TokenizerInfo(ctypes.Structure):
     _fields_ = [
         ("kind", ctypes.c_int32), ("vocab_size", ctypes.c_int32), ("n_added", ctypes.c_int32),
         ("unk_id", ctypes.c_int32), ("eos_id", ctypes.c_int32), ("max_piece_bytes", ctypes.c_int32),
-        ("word_table_entries", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 6),
+        ("word_table_entries", ctypes.c_uint64),
+        ("normalizer_flags", ctypes.c_int32),  # WordPiece: bit 0 keeps case, bit 1 keeps accents
+        ("reserved", ctypes.c_int32 * 5),
     ]
 
 
@@ -232,7 +235,9 @@ def check(rc):
 
 
 def tokenizer_info(path, data_dir=DATA_DIR):
-    """sdl_tokenizer_info_get: host-side load + checks of a tokenizer (no GPU)."""
+    """sdl_tokenizer_info_get: host-side load + checks of a tokenizer (no GPU).  A WordPiece
+    tokenizer's BertNormalizer setting comes back in normalizer_flags (bit 0: lowercase=false,
+    bit 1: strip_accents=false; 0 for bert-base-uncased's)."""
     info = TokenizerInfo()
     check(load().sdl_tokenizer_info_get(path.encode(), data_dir.encode(), ctypes.byref(info)))
     return info

@@ -10,6 +10,7 @@ captured here as tables by probing EVERY codepoint through the same project's
 Python binding (`tokenizers 0.22.2`, the version importable in this container):
 
   N(c)  = BertNormalizer(lowercase=True).normalize_str(chr(c))
+          (or with the setting the arguments name, below)
   class = how BertPreTokenizer treats N(c):
           DEL   N(c) == ""                (clean_text removals, lone Mn marks)
           WS    N(c) is only whitespace   (split + removed)
@@ -34,7 +35,19 @@ come out of a run in ccc order.  Probed the same way (N("x" + M226 + c + M216)):
   - a DEL char that still ends a run (a removed starter, e.g. an Mn with ccc 0):
     bit 4; other DEL chars (clean_text removals, Mn with ccc > 0) do not.
 Everything else either holds a starter (ends the run) or is removed.
+A setting that keeps accents runs no NFD, so nothing is ever reordered: the probe
+then finds no kept mark, and the table carries no bit-4 flag at all (every removed
+char would otherwise pass for a "removed starter" and send its word down the
+canonical-ordering paths for nothing).
+
+Without arguments this writes bert_uncased_unicode.bin (lowercase, strip accents).
+The other committed tables lie under tests/golden/bert_normalizer/, from where build()
+installs them into streaming_data_loader_amd/data/:
+  --no-lowercase --keep-accents   --out tests/golden/bert_normalizer/bert_cased_unicode.bin
+  --lowercase --keep-accents      --out tests/golden/bert_normalizer/bert_uncased_accents_unicode.bin
+  --no-lowercase --strip-accents  --out tests/golden/bert_normalizer/bert_cased_stripped_unicode.bin
 """
+import argparse
 import os
 import struct
 import sys
@@ -49,7 +62,16 @@ OTHER, WS, ISO, DEL = 0, 1, 2, 3
 
 
 def main():
-    norm = normalizers.BertNormalizer(lowercase=True)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--lowercase", dest="lowercase", action="store_true", default=True)
+    ap.add_argument("--no-lowercase", dest="lowercase", action="store_false")
+    ap.add_argument("--strip-accents", dest="strip_accents", action="store_true", default=None,
+                    help="default: follow --lowercase, as BertNormalizer does")
+    ap.add_argument("--keep-accents", dest="strip_accents", action="store_false")
+    ap.add_argument("--out", default=OUT)
+    args = ap.parse_args()
+    out_path = args.out
+    norm = normalizers.BertNormalizer(lowercase=args.lowercase, strip_accents=args.strip_accents)
     pre = pre_tokenizers.BertPreTokenizer()
     char_kind = {}
 
@@ -141,6 +163,9 @@ def main():
         e = entries[cp]
         if (e & 3) == OTHER and not (e & 4) and any(ord(x) in kept_ccc for x in norm.normalize_str(chr(cp))):
             entries[cp] |= 16  # precomposed: its decomposition holds kept marks
+    if not kept_ccc:
+        # nothing is ever reordered (no NFD): no run to end, so no flag
+        entries = [e & ~16 for e in entries]
     print(f"canonical ordering: {len(kept_ccc)} kept marks, "
           f"{sum(1 for e in entries if (e & 3) == DEL and e & 16)} removed starters, "
           f"{sum(1 for cp, e in enumerate(entries) if (e & 3) == OTHER and e & 16 and cp not in kept_ccc)} "
@@ -155,14 +180,14 @@ def main():
             block_index[blk] = bi
             blocks.append(blk)
         pages.append(bi)
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    with open(OUT, "wb") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "wb") as f:
         f.write(b"SDLU" + struct.pack("<IIII", 2, len(pages), len(blocks), len(pool)))
         f.write(struct.pack(f"<{len(pages)}H", *pages))
         for blk in blocks:
             f.write(struct.pack("<128I", *blk))
         f.write(bytes(pool))
-    print(f"pages={len(pages)} blocks={len(blocks)} pool={len(pool)} -> {OUT}", file=sys.stderr)
+    print(f"pages={len(pages)} blocks={len(blocks)} pool={len(pool)} -> {out_path}", file=sys.stderr)
 
 
 if __name__ == "__main__":
