@@ -81,8 +81,24 @@ typedef struct sdl_config {
                                 MLM masks = rand 0.8.5 position_base.shuffle (bert_data.rs:40-43;
                                 S <= 2048); span gap / size = rand_distr 0.4.3 StandardNormal,
                                 gap then size per pass (t5_data.rs:165-176) */
-    int32_t reserved[6];
+    int32_t mask_policy;     /* SDL_MASK_*: which positions of an MLM row are masked and what replaces
+                                them (DESIGN.md §3 "Masking policies").  0 = the reference's rule */
+    int32_t mask_per_mille;  /* policies 1 and 2: predictions per 1000 filled positions of a row (150);
+                                mask_length stays the row's maximum.  Ignored under policy 0 */
+    int32_t reserved[4];
 } sdl_config;
+
+/* sdl_config.mask_policy (MLM, rng_mode 0).  The two BERT policies never pick 0, mask_id or the
+ * framing ids ([CLS], [SEP]); they pick k = min(mask_length, max(1, (l * mask_per_mille + 500) /
+ * 1000)) of a row's l filled positions and replace 80 % by mask_id, 10 % by a uniform random id
+ * below the vocabulary size and leave 10 % (labels carry the id at every picked position).
+ * Both were carved out of reserved[6]: a zeroed field is the reference's rule, as before. */
+enum {
+    SDL_MASK_REFERENCE = 0,       /* BertData::mask_batch: mask_length draws of 0..S, non-zero ids -> mask_id */
+    SDL_MASK_BERT = 1,            /* BERT's create_pretraining_data.py, token by token */
+    SDL_MASK_BERT_WHOLE_WORD = 2  /* ... whole words: a WordPiece continuation piece ("##...") goes with
+                                     the piece before it; a word that no longer fits is skipped */
+};
 
 /* A finished batch: DataSet's Serialize view (bert_data.rs:106-145,
  * gpt_data.rs:53-62, t5_data.rs:235-249) as int32 row-major planes. */

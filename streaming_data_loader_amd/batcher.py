@@ -34,6 +34,10 @@ class BatchConfig:
 class Mask:
     mask_length: int
     mask: int = 103
+    # sdl_config.mask_policy / mask_per_mille (DESIGN.md §3 "Masking policies"): 0 the reference's
+    # rule, 1 BERT's 80/10/10 by token, 2 by whole word; per mille of a row's filled positions
+    mask_policy: int = 0
+    mask_per_mille: int = 150
 
 
 @dataclass
@@ -162,8 +166,10 @@ class DataSet:
         return {"input_ids": self.input_ids, "attention_mask": self.attention_mask, "labels": self.labels}
 
 
-def _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode):
-    """sdl_config for a ModelType/DataSetConfig pair (config.rs:43-62) -> (config, batch kind)."""
+def _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode, mask_policy=None,
+                   mask_per_mille=None):
+    """sdl_config for a ModelType/DataSetConfig pair (config.rs:43-62) -> (config, batch kind).
+    mask_policy / mask_per_mille, when given, override the Mask config's."""
     if isinstance(dataset_config, Mask):
         task, kind = native.SDL_TASK_MLM, "bert"
     elif isinstance(dataset_config, Gpt):
@@ -179,11 +185,16 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
     c.chunk = 1 if chunk else 0
     if isinstance(dataset_config, Mask):
         c.mask_length, c.mask_id = dataset_config.mask_length, dataset_config.mask
+        c.mask_policy, c.mask_per_mille = dataset_config.mask_policy, dataset_config.mask_per_mille
     if isinstance(dataset_config, Span):
         c.avg_span_gap, c.avg_span_size = dataset_config.avg_span_gap, dataset_config.avg_span_size
     if isinstance(dataset_config, MultiLabel):
         c.number_labels = dataset_config.number_labels
     c.seed, c.device, c.first_record, c.rng_mode = seed, device, first_record, rng_mode
+    if mask_policy is not None:
+        c.mask_policy = mask_policy
+    if mask_per_mille is not None:
+        c.mask_per_mille = mask_per_mille
     return c, kind
 
 
@@ -268,9 +279,11 @@ class _NativeBatcher(Batcher):
 
     def __init__(self, model_type: ModelType, batch_config: BatchConfig, dataset_config: DataSetConfig,
                  tokenizer: TokenizerConfig, chunk: bool = True, seed: int = 0, device: int = 0,
-                 first_record: int = 0, rng_mode: int = 0):
+                 first_record: int = 0, rng_mode: int = 0, mask_policy: Optional[int] = None,
+                 mask_per_mille: Optional[int] = None):
         L = native.load()
-        c, self.kind = _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode)
+        c, self.kind = _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode,
+                                      mask_policy, mask_per_mille)
         h = ctypes.c_void_p()
         native.check(L.sdl_batcher_create(ctypes.byref(c), tokenizer.path.encode(), native.DATA_DIR.encode(),
                                           ctypes.byref(h)))
@@ -492,9 +505,10 @@ class ShardedGenTokenizer:
 
     def __init__(self, model_type: ModelType, batch_config: BatchConfig, dataset_config: DataSetConfig,
                  tokenizer: TokenizerConfig, devices, chunk: bool = True, seed: int = 0, first_record: int = 0,
-                 rng_mode: int = 0):
+                 rng_mode: int = 0, mask_policy: Optional[int] = None, mask_per_mille: Optional[int] = None):
         L = native.load()
-        c, self.kind = _native_config(batch_config, dataset_config, chunk, seed, 0, first_record, rng_mode)
+        c, self.kind = _native_config(batch_config, dataset_config, chunk, seed, 0, first_record, rng_mode,
+                                      mask_policy, mask_per_mille)
         devs = (ctypes.c_int32 * len(devices))(*devices)
         m = ctypes.c_void_p()
         native.check(L.sdl_multi_create(ctypes.byref(c), tokenizer.path.encode(), native.DATA_DIR.encode(), devs,

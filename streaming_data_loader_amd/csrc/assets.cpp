@@ -155,6 +155,11 @@ static void build_vocab_table(HostTokenizer &t) {
     t.wp_lens[0].clear();
     t.wp_lens[1].clear();
     t.wp_long_pieces = false;
+    // whole-word masking (mask policy 2): which ids continue a word -- the piece's string starts
+    // with the continuing_subword_prefix, "##" (load_tokenizer refuses any other)
+    t.cont_bits.assign((n + 31) / 32, 0u);
+    for (size_t id = 0; id < n; ++id)
+        if (t.pieces[id].compare(0, 2, "##") == 0) t.cont_bits[id >> 5] |= 1u << (id & 31);
     for (size_t id = 0; id < n; ++id) {
         const std::string &s = t.pieces[id];
         if (s.empty() || last[s] != (int)id) continue;

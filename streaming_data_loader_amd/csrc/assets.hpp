@@ -38,6 +38,7 @@ struct HostTokenizer {
     int maxlen_first = 0, maxlen_cont = 0;
     std::vector<uint8_t> wp_lens[2];  // WordPiece: distinct payload lengths <= LW_MAX (non-"##", "##")
     bool wp_long_pieces = false;      // a payload longer than LW_MAX exists
+    std::vector<uint32_t> cont_bits;  // WordPiece: bit id set = piece id starts with "##" (<= 8 KiB: ids are u16)
     // WordPiece: the non-"##" pieces of <= WF_MAXLEN bytes again, in 16-byte slots (wp_first.hpp)
     std::vector<WfSlot> first_slots;
     uint32_t first_mask = 0, first_seed = 0;

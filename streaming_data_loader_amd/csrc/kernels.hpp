@@ -358,10 +358,22 @@ hipError_t launch_rows_direct(const DirectDst &d, const uint32_t *row_off, int64
                               const int32_t *am, const int32_t *tt, const int32_t *lab, int S, int LW,
                               const uint32_t *err0, const uint32_t *err1, uint32_t *stat, hipStream_t st);
 
+// The BERT masking policies of the MLM rows (sdl_config.mask_policy 1 / 2, DESIGN.md §3 "Masking
+// policies"): k_rows_policy's own argument.  Not fields of RowParams, DevTok or DevFirst: every
+// existing kernel takes those by value, and their layout is those kernels' machine code.
+struct MaskPolicy {
+    int32_t policy;             // 0 the reference's rule (k_rows), 1 tokens, 2 whole words
+    int32_t per_mille;          // predictions per 1000 filled positions (the row's cap stays mask_length)
+    uint32_t vocab_size;        // ids, added tokens included: the range of a random replacement
+    uint32_t pad;
+    const uint32_t *cont_bits;  // policy 2: bit i set = piece i continues a word ("##..."); ceil(vocab_size / 32) words
+};
+
+// mp (or null = the reference's rule): MLM under rng_mode 0 with mp->policy != 0 runs k_rows_policy
 hipError_t launch_rows(const RowParams &P, const TokSrc &src, const uint32_t *rec_tok, const uint32_t *rec_cnt,
                        const uint32_t *row_off, const uint32_t *row_rec, SegSel sel, int64_t rows_cap, RowOut out,
                        hipStream_t st,
-                       hipStream_t st_late = nullptr);
+                       hipStream_t st_late = nullptr, const MaskPolicy *mp = nullptr);
 // rng_mode 1 masks (pipeline.hip): the rows rand_pre_slot names (chunk 0 of every record, chunk 1
 // of long ones) from (seed, first_record + r, chunk) alone -- launched beside the tokenizer: swap
 // indices (lane per row) into jbuf [2 R, S], then the mask bits into P.mask_bits0 slots

@@ -557,6 +557,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MR >= 4 ? R
     }
 }
 
+// MLM rows under the BERT masking policies (MaskPolicy; row_policy_one): k_rows' geometry -- a
+// wave per row, four rows a block.  WHOLE: whole-word units (policy 2), with a wave's 256 MR
+// words of LDS for the units' sizes and picked flags; policy 1 is compiled without them.
+template <int MR, bool WHOLE, bool LISTS>
+__global__ __launch_bounds__(256) void k_rows_policy(RowParams P, MaskPolicy mp, TokSrc tok,
+                                                     const uint32_t *__restrict__ rec_tok,
+                                                     const uint32_t *__restrict__ rec_cnt,
+                                                     const uint32_t *__restrict__ row_off,
+                                                     const uint32_t *__restrict__ row_rec, SegSel sel,
+                                                     int64_t rows_cap, RowOut out) {
+    const int lane = lane_id();
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    __shared__ uint32_t s_unit[WHOLE ? 4 : 1][WHOLE ? 256 * MR : 1];
+    const RowSpan rs = row_span(sel, row_off, P.B, rows_cap);
+    const int64_t G = rs.g_real;
+    const int64_t g_end = out.direct.cap ? rs.g_real : rs.g_end;  // (direct: the host batch keeps its own padding)
+    for (int64_t g = rs.g_lo + (int64_t)blockIdx.x * 4 + wid; g < g_end; g += (int64_t)gridDim.x * 4)
+        row_policy_one<MR, WHOLE, LISTS>(P, mp, tok, rec_tok, rec_cnt, row_off, row_rec, g, G, out,
+                                         s_unit[WHOLE ? wid : 0], lane);
+}
+
 template <int MR>  // 0: no rows; else the call's rows too (d.rows: Philox mlm / clm)
 __global__ __launch_bounds__(SCAN_SMALL_NT) void k_downstream_small(SmallDown d, RowParams P,
                                                                     const uint64_t *__restrict__ off, int64_t R,
@@ -963,9 +984,38 @@ hipError_t launch_rows_direct(const DirectDst &d, const uint32_t *row_off, int64
 
 hipError_t launch_rows(const RowParams &P, const TokSrc &tok, const uint32_t *rec_tok, const uint32_t *rec_cnt,
                        const uint32_t *row_off, const uint32_t *row_rec, SegSel sel, int64_t rows_cap, RowOut out,
-                       hipStream_t st, hipStream_t st_late) {
+                       hipStream_t st, hipStream_t st_late, const MaskPolicy *mp) {
     if (!st_late) st_late = st;
     if (rows_cap == 0) return hipSuccess;
+    if (mp && mp->policy != 0) {  // the BERT policies: MLM on the Philox contract only
+        if (P.task != 0 || P.rng_mode != 0 || mp->policy < 1 || mp->policy > 2 || P.label_width != P.S ||
+            !out.labels || (mp->policy == 2 && !mp->cont_bits))
+            return hipErrorInvalidValue;
+        const int64_t want_p = (rows_cap + 3) / 4;
+        const unsigned grid_p = (unsigned)(want_p < 16384 ? want_p : 16384);
+        const int MRp = (P.S + 255) / 256;
+#define LAUNCH_POLICY_L(MM, WW, LL)                                                                                     \
+    hipLaunchKernelGGL((k_rows_policy<MM, WW, LL>), dim3(grid_p), dim3(256), 0, st, P, *mp, tok, rec_tok, rec_cnt,   \
+                       row_off, row_rec, sel, rows_cap, out)
+#define LAUNCH_POLICY(MM)                                                                                               \
+    do {                                                                                                              \
+        if (mp->policy == 2) {                                                                                        \
+            if (tok.lists) LAUNCH_POLICY_L(MM, true, true);                                                           \
+            else LAUNCH_POLICY_L(MM, true, false);                                                                    \
+        } else {                                                                                                      \
+            if (tok.lists) LAUNCH_POLICY_L(MM, false, true);                                                          \
+            else LAUNCH_POLICY_L(MM, false, false);                                                                   \
+        }                                                                                                             \
+    } while (0)
+        if (MRp <= 1) LAUNCH_POLICY(1);
+        else if (MRp <= 2) LAUNCH_POLICY(2);
+        else if (MRp <= 4) LAUNCH_POLICY(4);
+        else if (MRp <= 8) LAUNCH_POLICY(8);
+        else return hipErrorInvalidValue;
+#undef LAUNCH_POLICY
+#undef LAUNCH_POLICY_L
+        return hipGetLastError();
+    }
 constexpr int ROWS_GRID_CAP = 16384;
     const int64_t want = (rows_cap + 3) / 4;
     const unsigned grid = (unsigned)(want < ROWS_GRID_CAP ? want : ROWS_GRID_CAP);

@@ -8,6 +8,7 @@
 #include "device_util.hpp"
 #include "kernels.hpp"
 #include "list_index.hpp"
+#include "mlm_pick.hpp"
 
 namespace sdl {
 
@@ -321,81 +322,17 @@ __device__ __forceinline__ void store4(int32_t *p, int j0, int S, bool vec, int3
     }
 }
 
-// One row g of the call (a wave): BertData::put_data (+ mask_batch) / GptData::put_data framing and
-// planes; g >= G: a padding row of the last batch.  late_bits: the row's mask words (LATE).
-//
-// LISTS: the ids are read from the WordPiece chunk lists themselves (TokSrc, list_index.hpp), not
-// from a dense copy.  The row's first id lies in chunk c = row_chunk[g] (k_row_map).  One
-// coalesced load gives lane b the boundary chunk_off[c + b]; a row normally ends 3-4 chunks on, so
-// every id's chunk is a count of the few boundaries at or below its index (wave-uniform walk over
-// them) and its list's start a cross-lane read of the loaded boundaries: no dependent global load
-// between the boundaries and the ids.  A row that runs past the 63 loaded boundaries (a long run
-// of chunks without ids) searches chunk_off per lane instead -- any span.
-template <int MR, bool RM1, bool LATE, bool LISTS = false>
-__device__ __forceinline__ void row_one(const RowParams &P, const TokSrc &src,
-                                        const uint32_t *__restrict__ rec_tok, const uint32_t *__restrict__ rec_cnt,
-                                        const uint32_t *__restrict__ row_off, const uint32_t *__restrict__ row_rec,
-                                        int64_t g, int64_t G, const RowOut &out, const uint32_t *late_bits,
-                                        int lane) {
-    const int S = P.S;
-    const bool vec = (S & 3) == 0;  // 16-byte aligned rows
-    const bool vec_lb = (P.label_width & 3) == 0;
-    const DirectDst &dd = out.direct;
-    int32_t *ids_o = out.input_ids + g * S;
-    int32_t *am_o = out.attention_mask + g * S;
-    int32_t *tt_o = out.token_type_ids ? out.token_type_ids + g * S : nullptr;
-    int32_t *lb_o = out.labels ? out.labels + g * (int64_t)P.label_width : nullptr;
-    if (g < (int64_t)dd.cap) {  // a small push's row: straight into its host batch
-        const uint32_t slot = dd.base + (uint32_t)g, bi = slot >= dd.B ? 1u : 0u, row = slot - bi * dd.B;
-        ids_o = dd.ids[bi] + (size_t)row * S;
-        am_o = dd.am[bi] + (size_t)row * S;
-        tt_o = dd.tt[bi] ? dd.tt[bi] + (size_t)row * S : nullptr;
-        lb_o = dd.lab[bi] ? dd.lab[bi] + (size_t)row * P.label_width : nullptr;
-    }
-    if (g >= (int64_t)G) {  // rows of the last batch nobody filled: initial values
-#pragma unroll
-        for (int m = 0; m < MR; ++m) {
-            const int j0 = 256 * m + 4 * lane;
-            store4(ids_o, j0, S, vec, 0, 0, 0, 0);
-            store4(am_o, j0, S, vec, 1, 1, 1, 1);
-            if (tt_o) store4(tt_o, j0, S, vec, 0, 0, 0, 0);
-            if (lb_o) store4(lb_o, j0, P.label_width, vec_lb, -100, -100, -100, -100);
-        }
-        return;
-    }
-    // (LISTS) the row's first chunk c and the boundaries from it on, lane b's chunk_off[c + b]:
-    // loaded here, beside the record's fields, not after them (every row has a valid c)
-    const int64_t nl = LISTS ? src.n_lists : 0;
-    uint32_t c = 0, bnd = 0;  // bnd(0) <= the row's first id < bnd(1)
-    if constexpr (LISTS) {
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)src.row_chunk[g]);
-        bnd = src.chunk_off[(int64_t)c + lane < nl ? (int64_t)c + lane : nl];
-    }
-    const int64_t r = row_rec[g];
-    const uint32_t k = (uint32_t)(g - row_off[r]);
-    const uint32_t cnt = rec_cnt[r];
-    const uint32_t t0 = rec_tok[r];
-    const int64_t n = (int64_t)cnt + P.n_pre + P.n_post;
-    const int64_t base = P.chunk ? (int64_t)k * S : 0;
-    const int l = (int)((n - base) < S ? (n - base) : S);
-    // (rng_mode 1) the row's mask words, one dword a lane: walked beside the tokenizer
-    // (k_mask_bits_rec), else by the LATE pass (late_bits, LDS).  A row the first pass leaves to
-    // the LATE one returns only after its loads are issued: the mask words' load, a dependent
-    // step after row_rec / row_off, then overlaps the ids' (wave-uniform: a wave per row).
-    uint32_t mwd[MR];
-    bool mine = true;
-    if (RM1) {
-        const int64_t pre = rand_pre_slot(P, r, k);
-        mine = LATE || pre >= 0;
-        const uint32_t *bw = LATE ? late_bits : P.mask_bits0 + (pre >= 0 ? pre : 0) * (int64_t)P.mask_w;
-#pragma unroll
-        for (int m = 0; m < MR; ++m) {
-            const int j0 = 256 * m + 4 * lane;
-            mwd[m] = j0 < S && mine ? bw[j0 >> 5] : 0u;
-        }
-        if (LATE) __builtin_amdgcn_wave_barrier();  // (the LDS bits are rewritten by the wave's next rows)
-    }
-
+// The framed ids of a row's positions: id[m][w] is position 256 m + 4 lane + w of the row that
+// starts at framed index `base` of its record (cnt ids from t0 on) and fills l positions; 0 past
+// them.  LISTS: c / bnd / nl are the row's first chunk, the boundaries loaded from it on and the
+// chunks scanned (row_one).
+template <int MR>
+struct RowIds {
+    int32_t v[MR][4];
+};
+template <int MR, bool LISTS>
+__device__ __forceinline__ RowIds<MR> row_ids(const RowParams &P, const TokSrc &src, uint32_t c, uint32_t bnd,
+                                              int64_t nl, uint32_t t0, uint32_t cnt, int64_t base, int l, int lane) {
     int32_t id[MR][4];
     if constexpr (LISTS) {
         // the row's ids are [rel0, rel1) of the record's, [t_first, t_last] of the call's, and lie
@@ -480,6 +417,91 @@ __device__ __forceinline__ void row_one(const RowParams &P, const TokSrc &src,
             id[m][w] = v;
         }
     }
+    RowIds<MR> out;
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) out.v[m][w] = id[m][w];
+    return out;
+}
+
+// One row g of the call (a wave): BertData::put_data (+ mask_batch) / GptData::put_data framing and
+// planes; g >= G: a padding row of the last batch.  late_bits: the row's mask words (LATE).
+//
+// LISTS: the ids are read from the WordPiece chunk lists themselves (TokSrc, list_index.hpp), not
+// from a dense copy.  The row's first id lies in chunk c = row_chunk[g] (k_row_map).  One
+// coalesced load gives lane b the boundary chunk_off[c + b]; a row normally ends 3-4 chunks on, so
+// every id's chunk is a count of the few boundaries at or below its index (wave-uniform walk over
+// them) and its list's start a cross-lane read of the loaded boundaries: no dependent global load
+// between the boundaries and the ids.  A row that runs past the 63 loaded boundaries (a long run
+// of chunks without ids) searches chunk_off per lane instead -- any span.
+template <int MR, bool RM1, bool LATE, bool LISTS = false>
+__device__ __forceinline__ void row_one(const RowParams &P, const TokSrc &src,
+                                        const uint32_t *__restrict__ rec_tok, const uint32_t *__restrict__ rec_cnt,
+                                        const uint32_t *__restrict__ row_off, const uint32_t *__restrict__ row_rec,
+                                        int64_t g, int64_t G, const RowOut &out, const uint32_t *late_bits,
+                                        int lane) {
+    const int S = P.S;
+    const bool vec = (S & 3) == 0;  // 16-byte aligned rows
+    const bool vec_lb = (P.label_width & 3) == 0;
+    const DirectDst &dd = out.direct;
+    int32_t *ids_o = out.input_ids + g * S;
+    int32_t *am_o = out.attention_mask + g * S;
+    int32_t *tt_o = out.token_type_ids ? out.token_type_ids + g * S : nullptr;
+    int32_t *lb_o = out.labels ? out.labels + g * (int64_t)P.label_width : nullptr;
+    if (g < (int64_t)dd.cap) {  // a small push's row: straight into its host batch
+        const uint32_t slot = dd.base + (uint32_t)g, bi = slot >= dd.B ? 1u : 0u, row = slot - bi * dd.B;
+        ids_o = dd.ids[bi] + (size_t)row * S;
+        am_o = dd.am[bi] + (size_t)row * S;
+        tt_o = dd.tt[bi] ? dd.tt[bi] + (size_t)row * S : nullptr;
+        lb_o = dd.lab[bi] ? dd.lab[bi] + (size_t)row * P.label_width : nullptr;
+    }
+    if (g >= (int64_t)G) {  // rows of the last batch nobody filled: initial values
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            const int j0 = 256 * m + 4 * lane;
+            store4(ids_o, j0, S, vec, 0, 0, 0, 0);
+            store4(am_o, j0, S, vec, 1, 1, 1, 1);
+            if (tt_o) store4(tt_o, j0, S, vec, 0, 0, 0, 0);
+            if (lb_o) store4(lb_o, j0, P.label_width, vec_lb, -100, -100, -100, -100);
+        }
+        return;
+    }
+    // (LISTS) the row's first chunk c and the boundaries from it on, lane b's chunk_off[c + b]:
+    // loaded here, beside the record's fields, not after them (every row has a valid c)
+    const int64_t nl = LISTS ? src.n_lists : 0;
+    uint32_t c = 0, bnd = 0;  // bnd(0) <= the row's first id < bnd(1)
+    if constexpr (LISTS) {
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)src.row_chunk[g]);
+        bnd = src.chunk_off[(int64_t)c + lane < nl ? (int64_t)c + lane : nl];
+    }
+    const int64_t r = row_rec[g];
+    const uint32_t k = (uint32_t)(g - row_off[r]);
+    const uint32_t cnt = rec_cnt[r];
+    const uint32_t t0 = rec_tok[r];
+    const int64_t n = (int64_t)cnt + P.n_pre + P.n_post;
+    const int64_t base = P.chunk ? (int64_t)k * S : 0;
+    const int l = (int)((n - base) < S ? (n - base) : S);
+    // (rng_mode 1) the row's mask words, one dword a lane: walked beside the tokenizer
+    // (k_mask_bits_rec), else by the LATE pass (late_bits, LDS).  A row the first pass leaves to
+    // the LATE one returns only after its loads are issued: the mask words' load, a dependent
+    // step after row_rec / row_off, then overlaps the ids' (wave-uniform: a wave per row).
+    uint32_t mwd[MR];
+    bool mine = true;
+    if (RM1) {
+        const int64_t pre = rand_pre_slot(P, r, k);
+        mine = LATE || pre >= 0;
+        const uint32_t *bw = LATE ? late_bits : P.mask_bits0 + (pre >= 0 ? pre : 0) * (int64_t)P.mask_w;
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            const int j0 = 256 * m + 4 * lane;
+            mwd[m] = j0 < S && mine ? bw[j0 >> 5] : 0u;
+        }
+        if (LATE) __builtin_amdgcn_wave_barrier();  // (the LDS bits are rewritten by the wave's next rows)
+    }
+
+    const RowIds<MR> ids = row_ids<MR, LISTS>(P, src, c, bnd, nl, t0, cnt, base, l, lane);
+    const int32_t (&id)[MR][4] = ids.v;
     if (RM1 && !mine) return;  // (the LATE pass's row)
     // attention: 0 on [S-l, S) when l < S (reversed-range quirk, bert_data.rs:58-63 / gpt_data.rs:33-41)
     const int tail0 = l < S ? S - l : S;
@@ -554,6 +576,237 @@ __device__ __forceinline__ void row_one(const RowParams &P, const TokSrc &src,
             if (tt_o) store4(tt_o, j0, S, vec, 0, 0, 0, 0);
             store4(lb_o, j0, P.label_width, vec_lb, lab[0], lab[1], lab[2], lab[3]);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The BERT masking policies (sdl_config.mask_policy 1 / 2; DESIGN.md §3 "Masking policies").
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t max_u32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t min_u32r(uint32_t a, uint32_t b) { return a < b ? a : b; }
+// the wave, as mlm_pick.hpp asks for it: sums and minima over all lanes, uniform
+struct PickWave {
+    uint32_t l;
+    __device__ __forceinline__ uint32_t sum(uint32_t x) const {
+        return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_sum(x), 63);
+    }
+    __device__ __forceinline__ uint32_t min(uint32_t x) const {
+        DPP_SCAN_ID(x, min_u32r, 0xFFFFFFFFu);
+        return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+    }
+    __device__ __forceinline__ uint32_t lane() const { return l; }
+};
+
+// One MLM row g under policy 1 (WHOLE = false: every candidate a unit) or 2 (whole words), a wave:
+// row_one's geometry, framing, attention and stores; the pick and the 80/10/10 replacement are
+// the contract's.  A lane's masks are a bit per element, bit 4 m + w = position 256 m + 4 lane + w.
+// WHOLE: `lds` is the wave's 256 MR words -- the units' sizes (counted into their first position)
+// and then their picked flags, read back by the unit's other positions.
+template <int MR, bool WHOLE, bool LISTS>
+__device__ __forceinline__ void row_policy_one(const RowParams &P, const MaskPolicy &mp, const TokSrc &src,
+                                               const uint32_t *__restrict__ rec_tok,
+                                               const uint32_t *__restrict__ rec_cnt,
+                                               const uint32_t *__restrict__ row_off,
+                                               const uint32_t *__restrict__ row_rec, int64_t g, int64_t G,
+                                               const RowOut &out, uint32_t *lds, int lane) {
+    const int S = P.S;
+    const bool vec = (S & 3) == 0;
+    const DirectDst &dd = out.direct;
+    int32_t *ids_o = out.input_ids + g * S;
+    int32_t *am_o = out.attention_mask + g * S;
+    int32_t *tt_o = out.token_type_ids ? out.token_type_ids + g * S : nullptr;
+    int32_t *lb_o = out.labels + g * (int64_t)S;  // (mlm: label_width = S)
+    if (g < (int64_t)dd.cap) {  // a small push's row: straight into its host batch
+        const uint32_t slot = dd.base + (uint32_t)g, bi = slot >= dd.B ? 1u : 0u, row = slot - bi * dd.B;
+        ids_o = dd.ids[bi] + (size_t)row * S;
+        am_o = dd.am[bi] + (size_t)row * S;
+        tt_o = dd.tt[bi] ? dd.tt[bi] + (size_t)row * S : nullptr;
+        lb_o = dd.lab[bi] + (size_t)row * S;
+    }
+    if (g >= (int64_t)G) {  // rows of the last batch nobody filled: initial values
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            const int j0 = 256 * m + 4 * lane;
+            store4(ids_o, j0, S, vec, 0, 0, 0, 0);
+            store4(am_o, j0, S, vec, 1, 1, 1, 1);
+            if (tt_o) store4(tt_o, j0, S, vec, 0, 0, 0, 0);
+            store4(lb_o, j0, S, vec, -100, -100, -100, -100);
+        }
+        return;
+    }
+    const int64_t nl = LISTS ? src.n_lists : 0;
+    uint32_t c = 0, bnd = 0;
+    if constexpr (LISTS) {
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)src.row_chunk[g]);
+        bnd = src.chunk_off[(int64_t)c + lane < nl ? (int64_t)c + lane : nl];
+    }
+    const int64_t r = row_rec[g];
+    const uint32_t ck = (uint32_t)(g - row_off[r]);  // the row's chunk of its record
+    const uint32_t cnt = rec_cnt[r];
+    const uint32_t t0 = rec_tok[r];
+    const int64_t n = (int64_t)cnt + P.n_pre + P.n_post;
+    const int64_t base = P.chunk ? (int64_t)ck * S : 0;
+    const int l = (int)((n - base) < S ? (n - base) : S);
+    const RowIds<MR> ids = row_ids<MR, LISTS>(P, src, c, bnd, nl, t0, cnt, base, l, lane);
+    const int32_t (&id)[MR][4] = ids.v;
+    const int tail0 = l < S ? S - l : S;
+    const uint64_t rec = P.first_record + (uint64_t)r;
+    const PickWave wv{(uint32_t)lane};
+
+    // candidates: filled positions whose id is none of 0, mask_id and the framing ids
+    uint32_t cand = 0;
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int32_t v = id[m][w];
+            bool ex = v == 0 || v == P.mask_id;
+#pragma unroll
+            for (int q = 0; q < MAX_FRAME; ++q)
+                ex = ex || (q < P.n_pre && v == frame_id(P.pre, q)) || (q < P.n_post && v == frame_id(P.post, q));
+            if (256 * m + 4 * lane + w < l && !ex) cand |= 1u << (4 * m + w);
+        }
+    const int ncand = (int)wv.sum((uint32_t)__popc(cand));
+    int kb = (int)(((int64_t)l * mp.per_mille + 500) / 1000);
+    kb = kb < 1 ? 1 : kb;
+    kb = kb < P.mask_length ? kb : P.mask_length;
+    if (ncand == 0) kb = 0;
+
+    uint32_t sel = 0;  // the picked positions
+    if (kb > 0) {  // (wave-uniform)
+        uint32_t key[4 * MR];
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            const uint4 x = philox4x32_10(make_uint4((uint32_t)(64 * m + lane), ck, (uint32_t)rec, (uint32_t)(rec >> 32)),
+                                          (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+            key[4 * m] = x.x;
+            key[4 * m + 1] = x.y;
+            key[4 * m + 2] = x.z;
+            key[4 * m + 3] = x.w;
+        }
+        if constexpr (!WHOLE) {
+            // the kb smallest keys among the candidates (all of them if fewer): k_rows' select on
+            // keys pushed to the top off the candidates.  (A candidate whose own key is
+            // 0xFFFFFFFF would tie with those; 2^-32 a position, and no input steers a Philox word.)
+            uint32_t k2[MR][4];
+            bool s2[MR][4];
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) k2[m][w] = (cand >> (4 * m + w)) & 1u ? key[4 * m + w] : 0xFFFFFFFFu;
+            select_k_smallest_interp<MR>(k2, kb < ncand ? kb : ncand, ncand, s2);
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) sel |= s2[m][w] ? 1u << (4 * m + w) : 0u;
+            sel &= cand;
+        } else {
+            auto step = [] {  // one lane's LDS writes before the others' reads (a wave: program order)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            };
+            // continuation bits of the candidates' ids (the bitmap: 4 KiB for 30522 ids, L2-resident)
+            uint32_t cont = 0;
+#pragma unroll
+            for (int e = 0; e < 4 * MR; ++e) {
+                const uint32_t v = (uint32_t)id[e >> 2][e & 3];
+                const uint32_t wd = (cand >> e) & 1u && v < mp.vocab_size ? mp.cont_bits[v >> 5] : 0u;
+                cont |= ((wd >> (v & 31u)) & 1u) << e;
+            }
+            // is position j - 1 a candidate: the lane's own lower element, the previous lane's
+            // last of the round, or (lane 0) lane 63's last of the round before
+            const uint32_t xp = wave_prev(cand), x63 = (uint32_t)__builtin_amdgcn_readlane((int)cand, 63);
+            const uint32_t prev = ((cand << 1) & 0xEEEEEEEEu) |
+                                  (lane > 0 ? (xp >> 3) & 0x11111111u : (x63 << 1) & 0x11111110u);
+            const uint32_t start = cand & ~(cont & prev);
+            // every position's unit: the last start at or before it (position + 1; a max-scan,
+            // lane-local, then over the wave, carried across the rounds), counted into its size
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) lds[256 * m + 4 * lane + w] = 0u;
+            step();
+            uint32_t us[4 * MR], carry = 0;
+#pragma unroll
+            for (int m = 0; m < MR; ++m) {
+                uint32_t a[4], run = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    run = (start >> (4 * m + w)) & 1u ? (uint32_t)(256 * m + 4 * lane + w) + 1u : run;
+                    a[w] = run;
+                }
+                uint32_t incl = run;
+                DPP_SCAN(incl, max_u32);
+                const uint32_t before = max_u32(carry, wave_prev(incl));
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    us[4 * m + w] = max_u32(before, a[w]);  // (a candidate always has one: never 0 there)
+                    if ((cand >> (4 * m + w)) & 1u) atomicAdd(&lds[us[4 * m + w] ? us[4 * m + w] - 1u : 0u], 1u);
+                }
+                carry = max_u32(carry, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63));
+            }
+            step();
+            uint32_t size[4 * MR];
+#pragma unroll
+            for (int e = 0; e < 4 * MR; ++e)
+                size[e] = (start >> e) & 1u ? lds[256 * (e >> 2) + 4 * lane + (e & 3)] : 0u;
+            const uint32_t taken = mlm_pick_units<4 * MR>(key, size, (uint32_t)kb, wv);
+            step();
+#pragma unroll
+            for (int e = 0; e < 4 * MR; ++e)
+                if ((start >> e) & 1u) lds[256 * (e >> 2) + 4 * lane + (e & 3)] = (taken >> e) & 1u;
+            step();
+#pragma unroll
+            for (int e = 0; e < 4 * MR; ++e)
+                if ((cand >> e) & 1u) sel |= (lds[us[e] ? us[e] - 1u : 0u] & 1u) << e;
+            step();  // (the wave's next row rewrites the LDS)
+        }
+    }
+    // labels and the replacement: 80 % mask_id, 10 % a random id, 10 % unchanged, drawn only by
+    // the lanes that own a picked position
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+        const int j0 = 256 * m + 4 * lane;
+        const uint32_t s4 = (sel >> (4 * m)) & 15u;
+        int32_t v[4], lab[4], am[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            v[w] = id[m][w];
+            lab[w] = -100;
+            am[w] = j0 + w >= tail0 ? 0 : 1;
+        }
+        if (s4) {
+            const uint4 u4 = philox4x32_10(make_uint4((uint32_t)(64 * m + lane), ck | 0x20000000u, (uint32_t)rec,
+                                                      (uint32_t)(rec >> 32)),
+                                           (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+            const uint32_t u[4] = {u4.x, u4.y, u4.z, u4.w};
+            bool any_rand = false;
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+                any_rand = any_rand || ((s4 >> w) & 1u && u[w] >= 0xCCCCCCCDu && u[w] < 0xE6666667u);
+            uint32_t rr[4] = {0u, 0u, 0u, 0u};
+            if (any_rand) {
+                const uint4 r4 = philox4x32_10(make_uint4((uint32_t)(64 * m + lane), ck | 0x30000000u, (uint32_t)rec,
+                                                          (uint32_t)(rec >> 32)),
+                                               (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+                rr[0] = r4.x;
+                rr[1] = r4.y;
+                rr[2] = r4.z;
+                rr[3] = r4.w;
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+                if ((s4 >> w) & 1u) {
+                    lab[w] = v[w];
+                    if (u[w] < 0xCCCCCCCDu) v[w] = P.mask_id;
+                    else if (u[w] < 0xE6666667u) v[w] = (int32_t)__umulhi(rr[w], mp.vocab_size);
+                }
+        }
+        store4(ids_o, j0, S, vec, v[0], v[1], v[2], v[3]);
+        store4(am_o, j0, S, vec, am[0], am[1], am[2], am[3]);
+        if (tt_o) store4(tt_o, j0, S, vec, 0, 0, 0, 0);
+        store4(lb_o, j0, S, vec, lab[0], lab[1], lab[2], lab[3]);
     }
 }
 

@@ -261,6 +261,8 @@ struct sdl_batcher {
     DevBuf<int32_t> d_ascii_id;
     DevBuf<uint8_t> d_wp_lens;
     DevBuf<WfSlot> d_first_slots;
+    DevBuf<uint32_t> d_cont_bits;  // mask policy 2: the continuation bitmap (HostTokenizer::cont_bits)
+    MaskPolicy mpol{};             // sdl_config.mask_policy / mask_per_mille, as k_rows_policy takes them
     DevBuf<uint16_t> d_gpage, d_byte_id;
     DevBuf<uint8_t> d_gblock;
     DevBuf<MSlot> d_mslots;
@@ -495,6 +497,7 @@ struct sdl_batcher {
         }
         row_rec.ensure((size_t)std::max<int64_t>(rows_cap, 1));
         const bool rm1 = P.task == SDL_TASK_MLM && P.rng_mode == 1;
+        const bool policy = P.task == SDL_TASK_MLM && mpol.policy != 0;
         const int mask_w = (P.S + 31) / 32;
 
         RowParams p = P;
@@ -585,8 +588,9 @@ struct sdl_batcher {
                         uni ? (int64_t)UNI_STAGE : (int64_t)STAGE, wp ? 1 : 0, rec_local.p, rec_tok.p, rec_cnt.p,
                         rec_rows.p, row_off.p, row_rec.p, fused_done ? fuse_stat : nullptr,
                         uni ? uni_err.p : nullptr, 0, out};
-            // mlm (Philox) / clm rows in the same workgroup, no k_rows launch
-            d.rows = fused_done && !rm1 ? 1 : 0;
+            // mlm (Philox) / clm rows in the same workgroup, no k_rows launch (the BERT mask
+            // policies are k_rows_policy's alone: their small calls take one launch more)
+            d.rows = fused_done && !rm1 && !policy ? 1 : 0;
             return d;
         };
         auto downstream = [&](int k, hipStream_t s) {
@@ -647,7 +651,8 @@ struct sdl_batcher {
                     HIP_TRY(hipStreamWaitEvent(s, rand_ev[1], 0));
                     HIP_TRY(launch_rows(p, src, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s));
                 } else if (!rows_done) {
-                    HIP_TRY(launch_rows(p, src, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s));
+                    HIP_TRY(launch_rows(p, src, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel, rows_cap, out, s,
+                                        nullptr, policy ? &mpol : nullptr));
                 }
             }
             if (multi())
@@ -1004,6 +1009,8 @@ void sdl_config_default(sdl_config *c, int32_t task) {
     c->seed = 0;
     c->first_record = 0;
     c->device = 0;
+    c->mask_policy = SDL_MASK_REFERENCE;
+    c->mask_per_mille = 150;  // BERT's masked_lm_prob, used by policies 1 and 2 only
 }
 
 int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const char *data_dir, sdl_batcher **out) {
@@ -1024,6 +1031,16 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
     if (cfg->rng_mode != 0 && cfg->rng_mode != 1) return fail(SDL_ERR_ARG, "rng_mode must be 0 or 1");
     if (cfg->task == SDL_TASK_MLM && cfg->rng_mode == 1 && cfg->sequence_length > RAND_MAX_S)
         return fail(SDL_ERR_UNSUPPORTED, "rng_mode 1 supports sequence_length <= 2048");
+    if (cfg->mask_policy < SDL_MASK_REFERENCE || cfg->mask_policy > SDL_MASK_BERT_WHOLE_WORD)
+        return fail(SDL_ERR_ARG, "mask_policy must be 0 (reference), 1 (BERT) or 2 (BERT whole word)");
+    if (cfg->mask_policy != SDL_MASK_REFERENCE) {
+        if (cfg->task != SDL_TASK_MLM) return fail(SDL_ERR_ARG, "mask_policy 1 / 2 apply to the MLM task only");
+        if (cfg->mask_per_mille < 1 || cfg->mask_per_mille > 1000)
+            return fail(SDL_ERR_ARG, "mask_per_mille must be in [1, 1000] under mask_policy 1 / 2");
+        if (cfg->rng_mode == 1)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "mask_policy 1 / 2 need rng_mode 0: the reference's own draws define no such policy");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(SDL_ERR_NODEV, "no HIP device visible: the Batcher runs only on the GPU (no CPU fallback)");
@@ -1033,6 +1050,10 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
         h->cfg = *cfg;
         h->device = cfg->device;
         load_tokenizer(tokenizer_path, data_dir ? std::string(data_dir) : default_data_dir(), h->tok);
+        if (cfg->mask_policy == SDL_MASK_BERT_WHOLE_WORD && h->tok.kind != TOK_WORDPIECE)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "mask_policy 2 (SDL_MASK_BERT_WHOLE_WORD) needs a WordPiece tokenizer: whole words are "
+                        "not defined for byte-level BPE or Unigram pieces");
         HIP_TRY(hipSetDevice(h->device));
         {  // the handle's stream at the highest priority (stream2's background work yields to it)
             int least = 0, greatest = 0;
@@ -1227,6 +1248,12 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
         }
         P.seed = cfg->seed;
         P.rng_mode = cfg->rng_mode;
+        h->mpol = MaskPolicy{cfg->mask_policy, cfg->mask_per_mille, (uint32_t)t.pieces.size(), 0u, nullptr};
+        if (cfg->mask_policy == SDL_MASK_BERT_WHOLE_WORD) {
+            h->d_cont_bits.ensure(t.cont_bits.size());
+            HIP_TRY(hipMemcpy(h->d_cont_bits.p, t.cont_bits.data(), t.cont_bits.size() * 4, hipMemcpyHostToDevice));
+            h->mpol.cont_bits = h->d_cont_bits.p;
+        }
         if (t.kind == TOK_UNIGRAM) {
             // encode_mask framing for T5 (tokenizer_wrapper.rs:125-131): [eos] + template($A </s>) + [eos]
             P.n_pre = 1;

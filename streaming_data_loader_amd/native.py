@@ -18,6 +18,8 @@ GPT2_PROXY_TOKENIZER = os.path.join(ASSETS, "gpt2_proxy", "tokenizer.json")
 T5_PROXY_TOKENIZER = os.path.join(ASSETS, "t5_proxy", "tokenizer.json")
 
 SDL_TASK_MLM, SDL_TASK_CLM, SDL_TASK_SPAN, SDL_TASK_MULTI_LABEL, SDL_TASK_SINGLE_CLASS = 0, 1, 2, 3, 4
+# sdl_config.mask_policy: the reference's rule, BERT 80/10/10 by token, ... by whole word
+SDL_MASK_REFERENCE, SDL_MASK_BERT, SDL_MASK_BERT_WHOLE_WORD = 0, 1, 2
 
 # every symbol include/sdl_batcher.h declares
 EXPORTS = [
@@ -44,7 +46,9 @@ class Config(ctypes.Structure):
         ("mask_id", ctypes.c_int32), ("number_labels", ctypes.c_int32),
         ("avg_span_gap", ctypes.c_double), ("avg_span_size", ctypes.c_double),
         ("seed", ctypes.c_uint64), ("first_record", ctypes.c_uint64),
-        ("device", ctypes.c_int32), ("rng_mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6),
+        ("device", ctypes.c_int32), ("rng_mode", ctypes.c_int32),
+        ("mask_policy", ctypes.c_int32), ("mask_per_mille", ctypes.c_int32),  # SDL_MASK_*; policies 1 / 2
+        ("reserved", ctypes.c_int32 * 4),
     ]
 
 
