@@ -915,7 +915,9 @@ __global__ __launch_bounds__(256) void k_rows_to_host(const RowSeg *__restrict__
     int32_t *dst = plane == 0 ? sg.ids : plane == 1 ? sg.am : plane == 2 ? sg.tt : sg.lab;
     if (!src || !dst) return;
     const int W = plane == 3 ? LW : S;  // ints per row
-    const bool vec = (W & 3) == 0;
+    // (the planes of a host batch lie back to back: a label plane of 16-B rows behind id planes
+    // of odd S does not start on the 16-B grid -- span S = 65 with B = 3, or 8 multi-hot labels)
+    const bool vec = (W & 3) == 0 && ((uintptr_t)dst & 15u) == 0;
     for (uint32_t r = blockIdx.y; r < sg.n; r += gridDim.y) {
         const int32_t *s = src + (size_t)(sg.g0 + r) * W;
         int32_t *d = dst + (size_t)(sg.dst + r) * W;
@@ -964,7 +966,7 @@ __global__ __launch_bounds__(256) void k_rows_direct(DirectDst d, const uint32_t
         int32_t *dst = plane == 0 ? d.ids[bi] : plane == 1 ? d.am[bi] : plane == 2 ? d.tt[bi] : d.lab[bi];
         const int32_t *s = src + (size_t)g * W;
         int32_t *o = dst + (size_t)row * W;
-        if (vec) {
+        if (vec && ((uintptr_t)dst & 15u) == 0) {  // (a host batch's label plane: see k_rows_to_host)
             for (int j = 4 * lane; j < W; j += 256)
                 *reinterpret_cast<int4 *>(o + j) = *reinterpret_cast<const int4 *>(s + j);
         } else {

@@ -107,7 +107,7 @@ def assert_rows(got, G, wanted, what):
 
 # ---- the two paths, every MR instantiation ----------------------------------------------------------
 @pytest.mark.parametrize("policy", [1, 2])
-@pytest.mark.parametrize("S", [64, 66, 100, 128, 256, 320, 512, 1024, 2048])
+@pytest.mark.parametrize("S", [64, 65, 66, 100, 127, 128, 256, 257, 320, 512, 1023, 1024, 2048])
 def test_small_call_path(torch, native_lib, S, policy):  # noqa: F811
     texts, _, _ = unmasked("small", S, 0)
     wanted, infos = want("small", S, policy)
@@ -117,7 +117,8 @@ def test_small_call_path(torch, native_lib, S, policy):  # noqa: F811
 
 
 @pytest.mark.parametrize("policy", [1, 2])
-@pytest.mark.parametrize("S", [128, 512, 1024, 2048])  # (1024 / 2048: the MR 4 / 8 instantiations over lists)
+# (1024 / 2048: the MR 4 / 8 instantiations over lists; 254 / 1025 / 2047: the scalar stores, S & 3 = 2 / 1 / 3)
+@pytest.mark.parametrize("S", [128, 254, 512, 1024, 1025, 2047, 2048])
 def test_list_path(torch, native_lib, S, policy):  # noqa: F811
     texts, _, _ = unmasked("large", S, 0)
     wanted, infos = want("large", S, policy)

@@ -242,7 +242,8 @@ def test_long_lines_on_device(torch, native_lib):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("task,S,B,chunk", [("mlm", 128, 8, 20000), ("mlm", 512, 16, 65536), ("clm", 256, 4, 9000),
-                                            ("span", 128, 8, 30000), ("mlm", 128, 8, 1 << 30)])
+                                            ("span", 128, 8, 30000), ("mlm", 128, 8, 1 << 30),
+                                            ("clm", 127, 8, 7000)])  # (odd S: rows carried between chunks)
 def test_json_to_frames_equals_one_call(torch, native_lib, records, task, S, B, chunk):
     """sdl_json_to_frames (chunks cut at line ends, rows carried across chunks,
     copies overlapped on three streams) hands the sink exactly the frames of

@@ -49,7 +49,8 @@ def want_dict(task, rows, ids, am, tt, lab):
 @pytest.mark.parametrize("task,B,S,rows", [
     ("mlm", 4, 16, 4), ("mlm", 3, 12, 1), ("mlm", 2, 8, 0), ("clm", 3, 1024, 3), ("span", 2, 24, 1),
     ("multi-label", 5, 8, 5), ("multi-label", 1003, 4, 1001), ("mlm", 1000, 4, 1000), ("clm", 2, 2000, 2),
-    ("span", 1, 4003, 1)])
+    ("span", 1, 4003, 1),
+    ("mlm", 3, 5, 2), ("clm", 2, 2047, 1), ("span", 2, 101, 2), ("span", 3, 7, 3)])  # (odd widths, label width 25 / 1)
 def test_oracle_frame_loads_as_dataset(task, B, S, rows):
     LW, ids, am, tt, lab = planes(task, B, S, rows)
     frame = oracle_lib.pickle_dataset(task, B, S, LW, rows, ids, am, tt, lab)
