@@ -178,7 +178,12 @@ typedef struct sdl_device_rows {
                                  both: bert_data.rs:70-72, t5_data.rs:205-216) */
     uint32_t *d_tokenize_errors; /* device scalar (t5 tokenizer), 0 = ok; else bit 1: an item's ids
                                     exceeded their scratch, 2: id pool full, 3: long-item list full,
-                                    4: a whitespace-free run longer than 256 KiB normalized (dropped) */
+                                    4: a whitespace-free run longer than 256 KiB normalized (dropped);
+                                    (gpt2 tokenizer) bit 0: more long pieces than their list holds
+                                    (text_len / 64 + chunks + 1: the pieces past it get no ids);
+                                    null for WordPiece.  Every call clears it first.  The gpt2 flag
+                                    is reported here and checked by sdl_json_to_frames only: the
+                                    host record path (sdl_batcher_push*) forwards the t5 flags alone. */
 } sdl_device_rows;
 
 int sdl_process_device(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len,

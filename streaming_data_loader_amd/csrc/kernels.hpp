@@ -39,7 +39,11 @@ struct BpeLong {
 hipError_t launch_bpe_chunks(const DevTok &T, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
                              const uint32_t *ranges, uint32_t *tokc, uint32_t *chunk_cnt, uint32_t *chunk_ent,
                              uint32_t *rec_local, uint32_t *long_count, BpeLong *long_list, uint32_t long_cap,
-                             uint16_t *scratch, uint32_t *err, hipStream_t st);
+                             uint16_t *scratch, hipStream_t st);
+// long_count: u32 [BPE_LONG_WORDS] -- the long pieces listed, k_bpe_long's cursor, and the overflow
+// flag sdl_device_rows.d_tokenize_errors points at (bit 0: more long pieces than long_cap); one
+// memset at the start of every call clears all three
+constexpr int BPE_LONG_WORDS = 3, BPE_LONG_ERR = 2;
 
 // tokenize_unigram.hip: t5 (Precompiled + Unigram).  Same chunk outputs as the
 // other tokenizers; long items (non-ASCII / long words) are finished by two

@@ -291,7 +291,7 @@ struct sdl_batcher {
     DevBuf<float> o_f32;
     DevBuf<uint32_t> lab_err;
     // byte-level BPE long pieces
-    DevBuf<uint32_t> long_count, bpe_err, chunk_ent;
+    DevBuf<uint32_t> long_count, chunk_ent;
     DevBuf<BpeLong> long_list;
     DevBuf<uint16_t> long_scratch;
     // unigram long items
@@ -693,13 +693,12 @@ struct sdl_batcher {
         } else if (bpe) {
             // long pieces are > 64 bytes or run past their chunk's window (<= 1 per chunk)
             const uint32_t cap = (uint32_t)(N / 64 + n_chunks + 1);
-            long_count.ensure(2);  // (count, k_bpe_long cursor)
-            bpe_err.ensure(1);
+            long_count.ensure(BPE_LONG_WORDS);  // (count, k_bpe_long cursor, overflow flag)
             long_list.ensure(cap);
             long_scratch.ensure((size_t)N + 64);
             chunk_ent.ensure((size_t)n_chunks + 1);
             HIP_TRY(launch_bpe_chunks(dt, d_text, N, d_off, R, ranges.p, tokc.p, chunk_cnt.p, chunk_ent.p,
-                                      rec_local.p, long_count.p, long_list.p, cap, long_scratch.p, bpe_err.p, st));
+                                      rec_local.p, long_count.p, long_list.p, cap, long_scratch.p, st));
             downstream(0, st);
         } else if (!piped) {
             HIP_TRY(launch_wordpiece_chunks(dt, dfirst, tok.cased, d_text, N, d_off, R, ranges.p, lists, chunk_cnt.p,
@@ -1414,7 +1413,10 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
         out->labels = h->multi() ? nullptr : h->o_lab.p;
         out->labels_f32 = h->multi() ? h->o_f32.p : nullptr;
         out->d_label_errors = h->simple() ? h->lab_err.p : h->span() ? h->span_err.p : nullptr;
-        out->d_tokenize_errors = h->dt.kind == TOK_UNIGRAM ? h->uni_err.p : nullptr;
+        out->d_tokenize_errors = h->dt.kind == TOK_UNIGRAM    ? h->uni_err.p
+                                 : h->dt.kind == TOK_BYTE_BPE && h->long_count.p
+                                     ? h->long_count.p + BPE_LONG_ERR  // k_bpe_long's list overflow
+                                     : nullptr;
         out->d_rows = h->row_off.p + n_records;
         out->d_record_rows = h->rec_rows.p;
         out->d_tokens = h->chunk_off.p + (text_len + CHUNK - 1) / CHUNK;
@@ -2401,7 +2403,8 @@ int sdl_json_to_frames(sdl_batcher *h, const uint8_t *jsonl, uint64_t len, uint6
                 HIP_TRY(hipStreamSynchronize(sc));
                 hw[1] += since(t0);
                 if (h->pin_u32_err)
-                    throw CapacityError("t5 tokenizer capacity exceeded (flags " + std::to_string(h->pin_u32_err) + ")");
+                    throw CapacityError("tokenizer capacity exceeded (d_tokenize_errors flags " +
+                                        std::to_string(h->pin_u32_err) + ")");
                 G = g32;
             }
             // this pass's rows in its slot's planes: the carried rows (from the other slot), then the chunk's

@@ -1010,11 +1010,11 @@ __global__ __launch_bounds__(64) void k_bpe_long(DevTok T, const uint8_t *__rest
 hipError_t launch_bpe_chunks(const DevTok &T, const uint8_t *text, int64_t N, const uint64_t *off, int64_t R,
                              const uint32_t *ranges, uint32_t *tokc, uint32_t *chunk_cnt, uint32_t *chunk_ent,
                              uint32_t *rec_local, uint32_t *long_count, BpeLong *long_list, uint32_t long_cap,
-                             uint16_t *scratch, uint32_t *err, hipStream_t st) {
+                             uint16_t *scratch, hipStream_t st) {
     const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
-    if (n_chunks == 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(long_count, 0, 2 * sizeof(uint32_t), st);  // count, k_bpe_long's cursor
-    if (e != hipSuccess) return e;
+    // count, k_bpe_long's cursor, the overflow flag: each call reports its own
+    hipError_t e = hipMemsetAsync(long_count, 0, BPE_LONG_WORDS * sizeof(uint32_t), st);
+    if (e != hipSuccess || n_chunks == 0) return e;
     hipLaunchKernelGGL(k_bpe_chunks, dim3((unsigned)n_chunks), dim3(TOK_THREADS), 0, st, T, text, N, off, R, ranges,
                        tokc, chunk_cnt, chunk_ent, rec_local, long_count, long_list, long_cap);
     // one wave per long piece: the merges of one piece are a dependent chain of L2 round trips,
@@ -1024,7 +1024,7 @@ constexpr int BPE_LONG_GRID = 2048;
     const int64_t grid = std::min<int64_t>((int64_t)long_cap, BPE_LONG_GRID);
     if (grid > 0)
         hipLaunchKernelGGL(k_bpe_long, dim3((unsigned)grid), dim3(64), 0, st, T, text, N, off, R, long_count, long_list,
-                           long_cap, scratch, chunk_cnt, rec_local, err);
+                           long_cap, scratch, chunk_cnt, rec_local, long_count + BPE_LONG_ERR);
     return hipGetLastError();
 }
 

@@ -56,7 +56,7 @@ class DeviceResult:
         return int(v[0])
 
     def tokenize_errors(self):
-        """t5 tokenizer: capacity flags (include/sdl_batcher.h), 0 = ok."""
+        """t5 and gpt2 tokenizers: capacity flags (include/sdl_batcher.h), 0 = ok."""
         if not self.r.d_tokenize_errors:
             return 0
         v = np.zeros(1, np.uint32)
