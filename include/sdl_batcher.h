@@ -85,7 +85,10 @@ typedef struct sdl_config {
                                 them (DESIGN.md §3 "Masking policies").  0 = the reference's rule */
     int32_t mask_per_mille;  /* policies 1 and 2: predictions per 1000 filled positions of a row (150);
                                 mask_length stays the row's maximum.  Ignored under policy 0 */
-    int32_t reserved[4];
+    int32_t pack;            /* CLM, byte-level BPE: 0 = GenTokenizer's rows (every record cut into its own
+                                rows); 1 = documents concatenated with the end-of-text id and the stream
+                                cut into full rows ("Packed rows" below).  Carved out of reserved[4] */
+    int32_t reserved[3];
 } sdl_config;
 
 /* sdl_config.mask_policy (MLM, rng_mode 0).  The two BERT policies never pick 0, mask_id or the
@@ -117,6 +120,34 @@ typedef struct sdl_batch {
 } sdl_batch;
 
 typedef struct sdl_batcher sdl_batcher;
+
+/* ---- Packed rows (sdl_config.pack = 1; task clm, byte-level BPE) -----------
+ * No counterpart in the reference (like mask_policy): what GPT-2/3, Megatron and the HF
+ * group_texts recipes train on.  With t_r the tokenizer ids of record r (n_r of them, no
+ * framing), record r is kept when n_r >= 1 and n_r + 1 >= min_ids (min_ids = 0 keeps every
+ * non-empty document).  One call's stream is
+ *     carry ++ concat over kept r of (t_r ++ [eos])         eos = sdl_tokenizer_info.eos_id
+ * where carry is what the previous call on the handle left (< S ids, empty at first).  A stream of
+ * L ids gives G = L / S rows, row g = stream[g S, (g + 1) S), and stream[G S, L) is the new carry.
+ * Every emitted row has input_ids = labels = the stream ids (unshifted, as GptData) and
+ * attention_mask 1 everywhere.  A fourth plane, position_ids, restarts at 0 at the start of each
+ * row and after each document's eos (the eos belongs to its document): consumers derive
+ * cu_seqlens from position_ids == 0 where attention_mask == 1.  Document ends come from the record
+ * offsets, never from ids equal to eos, so a record holding the literal end-of-text string is
+ * still one document.  A flush turns a carry of c > 0 ids into one more row in the plain
+ * orientation -- columns < c as above, columns >= c input_ids 0, attention_mask 0, labels -100,
+ * position_ids 0 (not the reversed range of the reference's unpacked attention_mask) -- and
+ * empties the carry.  Rows from *d_rows to the next multiple of B hold the clm padding rows'
+ * initial values with position_ids 0.  d_record_rows[r] is the number of stream positions record r
+ * added (n_r + 1, or 0 when dropped); first_record and the seed are unused.
+ * Host path: sdl_batcher_push_many queues every full batch a call completes, in order;
+ * sdl_batcher_push is push_many of one record and returns the front of that queue (at most one
+ * batch; the rest wait for sdl_batcher_next); sdl_batcher_flush first turns a non-empty carry
+ * into the flush row, then pops the front of the queue -- full batches first, the partial one
+ * last -- and returns 0 once no filled row is left.  sdl_batch.token_type_ids stays NULL.
+ * sdl_multi_*: each shard's handle packs its own records, so packed rows, unlike unpacked ones,
+ * are not the rows one handle gives over the whole stream.  sdl_json_to_frames returns
+ * SDL_ERR_UNSUPPORTED; sdl_pickle_frames_device frames a packed call's three reference keys. */
 
 /* Defaults of the reference masking cases (masking_cases.rs:38-94) for `task`:
  * B=4096 S=128 chunk=1 min_ids=64 mask 15%/103, span 16.0/2.0, 9 labels. */
@@ -152,6 +183,9 @@ int sdl_batcher_next(sdl_batcher *h, sdl_batch *out);
  * (possibly partial, possibly empty).  1 = *out filled, 0 = none left. */
 int sdl_batcher_flush(sdl_batcher *h, sdl_batch *out);
 void sdl_batch_release(sdl_batch *b);
+/* pack = 1: the batch's position_ids plane [batch_size, sequence_length] (owned like the other
+ * planes); NULL for an unpacked batch. */
+const int32_t *sdl_batch_position_ids(const sdl_batch *b);
 
 /* ---- Device-resident bulk path (the measured hot path) -------------------
  * Tokenize + label every record of a device-resident arena in one sequence of
@@ -189,6 +223,14 @@ typedef struct sdl_device_rows {
 int sdl_process_device(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len,
                        const uint64_t *d_offsets, uint64_t n_records, uint64_t first_record,
                        void *stream, sdl_device_rows *out);
+
+/* pack = 1: the 0 or 1 flush row of the handle's carry into row 0 of the device planes (*d_rows
+ * says which), no host synchronisation; the carry is empty afterwards.  SDL_ERR_STATE when
+ * pack = 0. */
+int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out);
+/* pack = 1: the position_ids plane, device [rows_capacity, S], of the handle's last
+ * sdl_process_device / sdl_pack_flush_device call; NULL when pack = 0 or before the first call. */
+const int32_t *sdl_device_position_ids(sdl_batcher *h);
 
 /* sdl_process_device for the multi-label task with Label::Multi indices per
  * record: record r's indices are d_labels[d_label_offsets[r] .. d_label_offsets[r+1])

@@ -42,7 +42,9 @@ class Mask:
 
 @dataclass
 class Gpt:
-    pass
+    # sdl_config.pack (DESIGN.md §3 "Packed rows"): documents concatenated with the end-of-text id
+    # and the stream cut into full rows, with a position_ids plane; off = the reference's rows
+    pack: bool = False
 
 
 @dataclass
@@ -152,6 +154,7 @@ class DataSet:
     attention_mask: np.ndarray
     labels: np.ndarray
     token_type_ids: Optional[np.ndarray] = None
+    position_ids: Optional[np.ndarray] = None  # packed clm rows only (Gpt(pack=True))
 
     def to_dict(self):
         if self.kind == "bert-single":
@@ -163,7 +166,10 @@ class DataSet:
             # (Vec<i32> for Mask, Vec<f32> for MultiLabel)
             return {"input_ids": self.input_ids, "attention_mask": self.attention_mask,
                     "token_type_ids": self.token_type_ids, "labels": self.labels[:self.rows]}
-        return {"input_ids": self.input_ids, "attention_mask": self.attention_mask, "labels": self.labels}
+        d = {"input_ids": self.input_ids, "attention_mask": self.attention_mask, "labels": self.labels}
+        if self.position_ids is not None:
+            d["position_ids"] = self.position_ids
+        return d
 
 
 def _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode, mask_policy=None,
@@ -186,6 +192,8 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
     if isinstance(dataset_config, Mask):
         c.mask_length, c.mask_id = dataset_config.mask_length, dataset_config.mask
         c.mask_policy, c.mask_per_mille = dataset_config.mask_policy, dataset_config.mask_per_mille
+    if isinstance(dataset_config, Gpt):
+        c.pack = 1 if dataset_config.pack else 0
     if isinstance(dataset_config, Span):
         c.avg_span_gap, c.avg_span_size = dataset_config.avg_span_gap, dataset_config.avg_span_size
     if isinstance(dataset_config, MultiLabel):
@@ -230,9 +238,11 @@ def _dataset_from(b: native.Batch, kind: str) -> DataSet:
 
     i32 = (ctypes.c_int32, np.int32)
     labels = arr(b.labels_f32, B, LW, ctypes.c_float, np.float32) if bool(b.labels_f32) else arr(b.labels, B, LW, *i32)
+    pos = native.load().sdl_batch_position_ids(ctypes.byref(b))
     return DataSet(kind=kind, rows=b.rows, input_ids=arr(b.input_ids, B, S, *i32),
                    attention_mask=arr(b.attention_mask, B, S, *i32), labels=labels,
-                   token_type_ids=arr(b.token_type_ids, B, S, *i32) if bool(b.token_type_ids) else None)
+                   token_type_ids=arr(b.token_type_ids, B, S, *i32) if bool(b.token_type_ids) else None,
+                   position_ids=arr(pos, B, S, *i32) if bool(pos) else None)
 
 
 # ---- SimpleTransport (models/simple_transport.rs, simple_label.rs) ----------------

@@ -378,6 +378,29 @@ hipError_t launch_rows(const RowParams &P, const TokSrc &src, const uint32_t *re
                        const uint32_t *row_off, const uint32_t *row_rec, SegSel sel, int64_t rows_cap, RowOut out,
                        hipStream_t st,
                        hipStream_t st_late = nullptr, const MaskPolicy *mp = nullptr);
+// pack.hip: CLM rows packed from the concatenated document stream (sdl_config.pack = 1, DESIGN.md
+// §3 "Packed rows"), after launch_records.  A struct of its own, not fields of RowParams, DevTok or
+// DevFirst (see MaskPolicy): the unpacked kernels compile to what they were.
+struct PackParams {
+    const uint32_t *tok, *rec_tok, *rec_cnt;  // the dense ids and each record's first id / id count
+    uint32_t *rec_len;                        // out [R]: stream positions record r adds (ids + eos, 0 = dropped)
+    uint32_t *pk_off;                         // [R + 1]: where record r starts in the call's stream; [R] = its length
+    int64_t R, rows_cap;                      // rows_cap * S < 2^32
+    int32_t S, B, eos, min_ids;
+    const int32_t *carry_ids, *carry_pos;     // the carry the last call left (< S ids and their position_ids)
+    const uint32_t *carry_len;
+    int32_t *new_ids, *new_pos;               // the other half of the double buffer: this call's carry
+    uint32_t *new_len;
+    int32_t *ids, *am, *lab, *pos;            // planes [rows_cap, S]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// rec_len and pk_off[0] = the carry length: then launch_exclusive_scan(rec_len, pk_off, R, tmp, st, pk_off)
+hipError_t launch_pack_lengths(const PackParams &q, hipStream_t st);
+// the four planes (gather over the flat output index), then the new carry, its length and d_rows
+hipError_t launch_pack_rows(const PackParams &q, hipStream_t st);
+// the carry as one last row (0 rows when it is empty), rows < B of the planes; the new carry is empty
+hipError_t launch_pack_flush(const PackParams &q, hipStream_t st);
+
 // rng_mode 1 masks (pipeline.hip): the rows rand_pre_slot names (chunk 0 of every record, chunk 1
 // of long ones) from (seed, first_record + r, chunk) alone -- launched beside the tokenizer: swap
 // indices (lane per row) into jbuf [2 R, S], then the mask bits into P.mask_bits0 slots

@@ -29,6 +29,7 @@
 #include "../../include/sdl_batcher.h"
 #include "assets.hpp"
 #include "kernels.hpp"
+#include "pack_queue.hpp"
 
 using namespace sdl;
 
@@ -144,6 +145,7 @@ struct HostBatch {
     float *f32 = nullptr;  // MultiLabel: [B, number_labels]
     int rows = 0;
     int B, S, LW;
+    bool tt_is_pos = false;  // pack = 1 (clm): the fourth plane holds position_ids, not token types
     static size_t block_bytes(int B, int S, int LW, bool with_tt) {
         return 4 * (size_t)B * ((size_t)S * (with_tt ? 3 : 2) + (size_t)LW);
     }
@@ -175,7 +177,7 @@ struct HostBatch {
         if (r0 >= r1) return;
         std::fill(ids + r0 * S, ids + r1 * S, 0);
         std::fill(am + r0 * S, am + r1 * S, 1);
-        if (tt) std::fill(tt + r0 * S, tt + r1 * S, 0);
+        if (tt) std::fill(tt + r0 * S, tt + r1 * S, 0);  // (token types and position_ids alike)
         if (lab) std::fill(lab + r0 * LW, lab + r1 * LW, -100);
         if (f32) std::fill(f32 + r0 * LW, f32 + r1 * LW, 0.f);
     }
@@ -447,11 +449,79 @@ struct sdl_batcher {
     bool simple() const { return multi() || single(); }  // SimpleBatcher (simple_batcher.rs)
     bool span() const { return P.task == SDL_TASK_SPAN; }
     bool with_tt() const { return P.task == SDL_TASK_MLM || simple(); }
+    // sdl_config.pack = 1: clm rows cut from the concatenated document stream (pack.hip).  The
+    // position_ids travel through the token-type plumbing clm does not use (o_tt, RowSeg.tt,
+    // HostBatch.tt); the public token_type_ids stays NULL
+    bool pack() const { return cfg.pack == 1; }
+    bool plane4() const { return with_tt() || pack(); }
 
     std::shared_ptr<BatchPool> pool;
     HostBatch *new_batch() {
-        if (!pool) pool = std::make_shared<BatchPool>(HostBatch::block_bytes(P.B, P.S, P.label_width, with_tt()));
-        return new HostBatch(pool, P.B, P.S, P.label_width, with_tt(), multi());
+        if (!pool) pool = std::make_shared<BatchPool>(HostBatch::block_bytes(P.B, P.S, P.label_width, plane4()));
+        HostBatch *b = new HostBatch(pool, P.B, P.S, P.label_width, plane4(), multi());
+        b->tt_is_pos = pack();
+        return b;
+    }
+
+    // pack = 1: the carry between calls, double buffered (ids and position_ids, S each per half),
+    // and pk_meta = {rows of the last call, length of half 0, length of half 1}; the host only
+    // knows which half is current -- it flips per call, the lengths stay on the device
+    DevBuf<int32_t> pk_carry;
+    DevBuf<uint32_t> pk_meta, pk_off;
+    int pk_cur = 0;
+    bool pk_ran = false;
+    PackParams pack_params(int64_t R, int64_t rows_cap) {
+        const size_t S = (size_t)P.S;
+        const int cur = pk_cur, nxt = cur ^ 1;
+        PackParams q{};
+        q.tok = tok_ids.p;
+        q.rec_tok = rec_tok.p;
+        q.rec_cnt = rec_cnt.p;
+        q.rec_len = rec_rows.p;
+        q.pk_off = pk_off.p;
+        q.R = R;
+        q.rows_cap = rows_cap;
+        q.S = P.S;
+        q.B = P.B;
+        q.eos = tok.eos_id;
+        q.min_ids = P.min_ids;
+        q.carry_ids = pk_carry.p + (size_t)cur * 2 * S;
+        q.carry_pos = q.carry_ids + S;
+        q.carry_len = pk_meta.p + 1 + cur;
+        q.new_ids = pk_carry.p + (size_t)nxt * 2 * S;
+        q.new_pos = q.new_ids + S;
+        q.new_len = pk_meta.p + 1 + nxt;
+        q.ids = o_ids.p;
+        q.am = o_am.p;
+        q.lab = o_lab.p;
+        q.pos = o_tt.p;
+        q.d_rows = pk_meta.p;
+        return q;
+    }
+    // the call's rows from rec_tok / rec_cnt (after launch_records): packed lengths, their scan
+    // seeded with the carry length, the gather and the new carry -- no host synchronisation
+    void run_pack(int64_t R, int64_t rows_cap, hipStream_t st) {
+        pk_off.ensure((size_t)R + 1);
+        const PackParams q = pack_params(R, rows_cap);
+        HIP_TRY(launch_pack_lengths(q, st));
+        HIP_TRY(launch_exclusive_scan(rec_rows.p, pk_off.p, R, scan_tmp.p, st, pk_off.p));
+        HIP_TRY(launch_pack_rows(q, st));
+        pk_cur ^= 1;
+        pk_ran = true;
+    }
+    // the flush row into row 0 of the planes (0 rows when the carry is empty); empties the carry
+    void run_pack_flush(hipStream_t st) {
+        const int64_t rows_cap = P.B;
+        const size_t plane = (size_t)rows_cap * P.S;
+        o_ids.ensure(plane);
+        o_am.ensure(plane);
+        o_tt.ensure(plane);
+        o_lab.ensure(plane);
+        HIP_TRY(launch_pack_flush(pack_params(0, rows_cap), st));
+        pk_cur ^= 1;
+        pk_ran = true;
+        last_rows_cap = rows_cap;
+        last_R = 0;
     }
 
     int64_t rows_capacity(int64_t N, int64_t R) const {
@@ -460,6 +530,7 @@ struct sdl_batcher {
         // ids <= bytes (WordPiece, BPE); Unigram: <= 2 * bytes + the pool slack
         const int64_t ids = dt.kind == TOK_UNIGRAM ? 2 * N + 1024 * 1024 : N;
         int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
+        if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
         return (cap + P.B - 1) / P.B * P.B;
     }
 
@@ -467,6 +538,9 @@ struct sdl_batcher {
                     hipStream_t st, const uint32_t *d_labels = nullptr, const uint64_t *d_label_off = nullptr) {
         const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
         const int64_t rows_cap = rows_capacity(N, R);
+        // (pack.hip indexes the planes and the stream with 32 bits)
+        if (pack() && rows_cap * P.S > ((int64_t)1 << 32) - 4096)
+            throw CapacityError("pack: the call's rows exceed 2^32 positions");
         ranges.ensure((size_t)std::max<int64_t>(n_chunks, 1) * 3);
         // a chunk's list: STAGE u16 (WordPiece), STAGE / UNI_STAGE u32 entries (BPE / Unigram)
         const bool wp = dt.kind != TOK_BYTE_BPE && dt.kind != TOK_UNIGRAM;
@@ -487,7 +561,7 @@ struct sdl_batcher {
         const size_t plane = (size_t)std::max<int64_t>(rows_cap, 1) * P.S;
         o_ids.ensure(plane);
         o_am.ensure(plane);
-        if (with_tt()) o_tt.ensure(plane);
+        if (plane4()) o_tt.ensure(plane);
         if (multi()) {
             o_f32.ensure((size_t)std::max<int64_t>(rows_cap, 1) * P.label_width);
             lab_err.ensure(1);
@@ -530,7 +604,8 @@ struct sdl_batcher {
         auto mark = [&](int i) {
             if (profiling) HIP_TRY(hipEventRecord(ev[i], st));
         };
-        const bool small = !piped && !profiling && n_chunks <= SMALL_CHUNKS && R <= 8192;
+        // (pack = 1 takes the plain one-segment sequence up to launch_records, then pack.hip)
+        const bool small = !piped && !profiling && !pack() && n_chunks <= SMALL_CHUNKS && R <= 8192;
         // WordPiece, large calls: k_rows reads the chunk lists themselves -- no dense copy of the
         // ids (span's rows kernels and the small-call kernels read the dense array)
         const bool from_lists = wp && !small && !span();
@@ -619,6 +694,11 @@ struct sdl_batcher {
             HIP_TRY(launch_records(p, d_off, R, N, chunk_off.p, n_chunks, rec_local.p, rec_tok.p, rec_cnt.p, rec_rows.p,
                                    sel, s));
             if (!piped) mark(5);
+            if (pack()) {  // rec_tok / rec_cnt exist: the stream's rows instead of row scan, row map and k_rows
+                mark(6);
+                run_pack(R, rows_cap, s);
+                return;
+            }
             if (piped) HIP_TRY(launch_scan_range(rec_rows.p, row_off.p, seg_rb.p, k, s));
             else HIP_TRY(launch_exclusive_scan(rec_rows.p, row_off.p, R, scan_tmp.p, s));
             // (segment k's rows read lists and offsets of chunks < cz only: all written by now)
@@ -741,6 +821,50 @@ struct sdl_batcher {
     int64_t last_segments = 1;
     int64_t last_rows_cap = 0, last_R = 0;
 
+    // pack = 1, host path: the rows the last packed call (or flush) left in the device planes go
+    // to the working batch and fresh ones behind it (pack_queue.hpp); every batch they fill is
+    // queued, in order.  One synchronisation for the row count, one for the copy.
+    void queue_packed_rows() {
+        pin_u32.ensure(4);
+        HIP_TRY(hipMemcpyAsync(pin_u32.p, pk_meta.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const uint32_t G = pin_u32.p[0];
+        if (store.empty()) store.push_back(new_batch());
+        const PackPlan plan = pack_queue_plan((uint32_t)store.back()->rows, (uint32_t)P.B, G);
+        if (plan.segs.empty()) return;
+        std::vector<HostBatch *> bs{store.back()};
+        store.pop_back();
+        struct Unwind {  // (a throw below: the batches not yet queued are freed)
+            std::vector<HostBatch *> &v;
+            ~Unwind() {
+                for (HostBatch *b : v) delete b;
+            }
+        } unwind{bs};
+        while (bs.size() < (size_t)plan.completed + 1) bs.push_back(new_batch());
+        seg_pin.ensure(plan.segs.size());
+        seg_dev.ensure(plan.segs.size());
+        uint32_t nmax = 0;
+        for (size_t i = 0; i < plan.segs.size(); ++i) {
+            const PackSeg &q = plan.segs[i];
+            HostBatch *b = bs[q.batch];
+            seg_pin.p[i] = RowSeg{b->on_dev(b->ids), b->on_dev(b->am), b->on_dev(b->tt), b->on_dev(b->lab), q.g0, q.n,
+                                  q.dst, 0u};
+            nmax = std::max(nmax, q.n);
+        }
+        HIP_TRY(hipMemcpyAsync(seg_dev.p, seg_pin.p, sizeof(RowSeg) * plan.segs.size(), hipMemcpyHostToDevice, stream));
+        HIP_TRY(launch_rows_to_host(seg_dev.p, (int)plan.segs.size(), nmax, o_ids.p, o_am.p, o_tt.p, o_lab.p, P.S,
+                                    P.label_width, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (uint32_t k = 0; k < plan.completed; ++k) {
+            bs[k]->rows = P.B;
+            outbox.push_back(bs[k]);
+            bs[k] = nullptr;
+        }
+        bs.back()->rows = (int)plan.fill;
+        store.push_back(bs.back());
+        bs.back() = nullptr;
+    }
+
     // H2D a host arena, run the device path, bring back the rows; then play
     // GenTokenizer's queue over the per-record row counts.
     void process_host(const uint8_t *arena, const uint64_t *offsets, int64_t R, const uint32_t *labels,
@@ -790,7 +914,7 @@ struct sdl_batcher {
         // Small calls (a per-record push): the rows go straight to the back batch
         // and a pre-allocated next one in the same pass, and the row offsets and
         // error words come back through mapped memory -- one synchronisation.
-        const bool direct = R <= 4096 && N <= ((int64_t)1 << 20) && !store.empty() && !profiling;
+        const bool direct = R <= 4096 && N <= ((int64_t)1 << 20) && !store.empty() && !profiling && !pack();
         uint32_t cap = 0;
         const uint32_t *stat;
         DirectDst dd{};
@@ -826,6 +950,14 @@ struct sdl_batcher {
                        stream, d_labels, d_label_off);
         }
         fuse_stat = nullptr;
+        if (pack()) {  // the stream's rows fill the queue's batches; no per-record cadence
+            hc.lap("enqueue");
+            queue_packed_rows();
+            hc.lap("h2d+kernels+d2h");
+            hc.report(N, 0, pool ? pool->fresh : 0);
+            n_records += (uint64_t)R;
+            return;
+        }
         if (direct) {
             if (!fused_done)
                 HIP_TRY(launch_rows_direct(dd, row_off.p, R, o_ids.p, o_am.p, with_tt() ? o_tt.p : nullptr,
@@ -924,7 +1056,7 @@ void fill_batch(const sdl_batcher *h, HostBatch *b, sdl_batch *out) {
     b->init_tail();
     out->input_ids = b->ids;
     out->attention_mask = b->am;
-    out->token_type_ids = b->tt;
+    out->token_type_ids = b->tt_is_pos ? nullptr : b->tt;  // (position_ids: sdl_batch_position_ids)
     out->labels = b->lab;
     out->labels_f32 = b->f32;
     out->owner_ = b;
@@ -1040,6 +1172,8 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             return fail(SDL_ERR_UNSUPPORTED,
                         "mask_policy 1 / 2 need rng_mode 0: the reference's own draws define no such policy");
     }
+    if (cfg->pack != 0 && cfg->pack != 1) return fail(SDL_ERR_ARG, "pack must be 0 (off) or 1 (packed rows)");
+    if (cfg->pack == 1 && cfg->task != SDL_TASK_CLM) return fail(SDL_ERR_ARG, "pack = 1 applies to the CLM task only");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(SDL_ERR_NODEV, "no HIP device visible: the Batcher runs only on the GPU (no CPU fallback)");
@@ -1053,6 +1187,10 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             return fail(SDL_ERR_UNSUPPORTED,
                         "mask_policy 2 (SDL_MASK_BERT_WHOLE_WORD) needs a WordPiece tokenizer: whole words are "
                         "not defined for byte-level BPE or Unigram pieces");
+        if (cfg->pack == 1 && (h->tok.kind != TOK_BYTE_BPE || h->tok.eos_id < 0))
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pack = 1 needs a byte-level BPE tokenizer with an <|endoftext|> id: packed rows are "
+                        "not built for WordPiece or Unigram tokenizers");
         HIP_TRY(hipSetDevice(h->device));
         {  // the handle's stream at the highest priority (stream2's background work yields to it)
             int least = 0, greatest = 0;
@@ -1276,6 +1414,12 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             P.post[1] = t.sep_id;
             P.post[2] = t.sep_id;
         }
+        if (h->pack()) {  // an empty carry in both halves
+            h->pk_carry.ensure(4 * (size_t)P.S);
+            h->pk_meta.ensure(4);
+            HIP_TRY(hipMemsetAsync(h->pk_meta.p, 0, 4 * sizeof(uint32_t), h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));  // (the first call may come on a caller's stream)
+        }
         h->store.push_back(h->new_batch());  // GenTokenizer::new: first DataSet
     } catch (HipError &e) {
         return fail(SDL_ERR_HIP, e.what());
@@ -1311,6 +1455,14 @@ int sdl_batcher_push(sdl_batcher *h, const uint8_t *utf8, size_t len, const uint
         uint64_t loffs[2] = {0, (uint64_t)n_labels};
         const size_t before = h->outbox.size();
         h->process_host(utf8 ? utf8 : (const uint8_t *)"", offs, 1, labels, loffs);
+        if (h->pack()) {  // push_many of one record: the front of the queue, the rest wait for sdl_batcher_next
+            if (h->outbox.empty()) return 0;
+            HostBatch *b = h->outbox.front();
+            h->outbox.pop_front();
+            if (out) fill_batch(h, b, out);
+            else delete b;
+            return 1;
+        }
         if (h->outbox.size() > before) {
             HostBatch *b = h->outbox.back();
             h->outbox.pop_back();
@@ -1374,6 +1526,29 @@ int sdl_batcher_next(sdl_batcher *h, sdl_batch *out) {
 
 int sdl_batcher_flush(sdl_batcher *h, sdl_batch *out) {
     if (!h || !out) return fail(SDL_ERR_ARG, "null argument");
+    if (h->pack()) {
+        // the carry becomes the flush row behind the queued rows; then the front of the queue:
+        // the full batches first, the partial one last, nothing once no filled row is left
+        try {
+            h->run_pack_flush(h->stream);
+            h->queue_packed_rows();
+        } catch (HipError &e) {
+            return fail(SDL_ERR_HIP, e.what());
+        } catch (std::exception &e) {
+            return fail(SDL_ERR_ARG, e.what());
+        }
+        HostBatch *b = nullptr;
+        if (!h->outbox.empty()) {
+            b = h->outbox.front();
+            h->outbox.pop_front();
+        } else if (!h->store.empty() && h->store.front()->rows > 0) {
+            b = h->store.front();
+            h->store.pop_front();
+        }
+        if (!b) return 0;
+        fill_batch(h, b, out);
+        return 1;
+    }
     if (h->store.empty()) return 0;  // GenTokenizer::get_working_batch = store.pop_front()
     HostBatch *b = h->store.front();
     h->store.pop_front();
@@ -1387,6 +1562,12 @@ void sdl_batch_release(sdl_batch *b) {
     if (!b || !b->owner_) return;
     delete static_cast<HostBatch *>(b->owner_);
     std::memset(b, 0, sizeof(*b));
+}
+
+const int32_t *sdl_batch_position_ids(const sdl_batch *b) {
+    if (!b || !b->owner_) return nullptr;
+    const HostBatch *hb = static_cast<const HostBatch *>(b->owner_);
+    return hb->tt_is_pos ? hb->tt : nullptr;
 }
 
 int sdl_process_device(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len, const uint64_t *d_offsets,
@@ -1417,7 +1598,7 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
                                  : h->dt.kind == TOK_BYTE_BPE && h->long_count.p
                                      ? h->long_count.p + BPE_LONG_ERR  // k_bpe_long's list overflow
                                      : nullptr;
-        out->d_rows = h->row_off.p + n_records;
+        out->d_rows = h->pack() ? h->pk_meta.p : h->row_off.p + n_records;
         out->d_record_rows = h->rec_rows.p;
         out->d_tokens = h->chunk_off.p + (text_len + CHUNK - 1) / CHUNK;
         out->rows_capacity = (uint64_t)h->last_rows_cap;
@@ -1429,6 +1610,28 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
         return fail(SDL_ERR_ARG, e.what());
     }
 }
+
+int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out) {
+    if (!h || !out) return fail(SDL_ERR_ARG, "null argument");
+    if (!h->pack()) return fail(SDL_ERR_STATE, "sdl_pack_flush_device needs a handle created with pack = 1");
+    try {
+        h->run_pack_flush(stream ? (hipStream_t)stream : h->stream);
+        std::memset(out, 0, sizeof(*out));
+        out->input_ids = h->o_ids.p;
+        out->attention_mask = h->o_am.p;
+        out->labels = h->o_lab.p;
+        out->d_rows = h->pk_meta.p;
+        out->rows_capacity = (uint64_t)h->last_rows_cap;
+        out->label_width = h->P.label_width;
+        return SDL_OK;
+    } catch (HipError &e) {
+        return fail(SDL_ERR_HIP, e.what());
+    } catch (std::exception &e) {
+        return fail(SDL_ERR_ARG, e.what());
+    }
+}
+
+const int32_t *sdl_device_position_ids(sdl_batcher *h) { return h && h->pack() && h->pk_ran ? h->o_tt.p : nullptr; }
 
 int sdl_json_text_device(sdl_batcher *h, const uint8_t *d_jsonl, uint64_t len, void *stream, sdl_json_text *out) {
     if (!h || !out || (!d_jsonl && len)) return fail(SDL_ERR_ARG, "null argument");
@@ -2279,6 +2482,10 @@ int sdl_json_to_frames(sdl_batcher *h, const uint8_t *jsonl, uint64_t len, uint6
     const int task = h->cfg.task;
     if (task != SDL_TASK_MLM && task != SDL_TASK_CLM && task != SDL_TASK_SPAN)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: JSON lines carry text only (mlm, clm, span)");
+    if (h->pack())
+        return fail(SDL_ERR_UNSUPPORTED,
+                    "sdl_json_to_frames: pack = 1 is not supported (the rows carried between chunks would need "
+                    "the id carry too)");
     if (chunk_bytes == 0) chunk_bytes = (uint64_t)8 << 20;
     if (chunk_bytes >= (1ull << 31)) return fail(SDL_ERR_CAPACITY, "chunk_bytes must be < 2 GiB");
     try {

@@ -22,8 +22,9 @@ class _CudaView:
 
 
 class DeviceResult:
-    def __init__(self, handle, rows_struct, n_records, S, B=None, device=0, stream=0):
+    def __init__(self, handle, rows_struct, n_records, S, B=None, device=0, stream=0, pos_ptr=None):
         self.h = handle
+        self.pos_ptr = pos_ptr  # packed clm rows: the position_ids plane (sdl_device_position_ids)
         self.r = rows_struct
         self.n_records = n_records
         self.S = S
@@ -79,6 +80,14 @@ class DeviceResult:
         lab = get(self.r.labels_f32, LW, np.float32) if self.r.labels_f32 else get(self.r.labels, LW)
         return (get(self.r.input_ids, S), get(self.r.attention_mask, S), get(self.r.token_type_ids, S), lab)
 
+    def position_ids(self, n_rows=None):
+        """Packed clm rows (DeviceBatcher(pack=1)): the position_ids plane as numpy [n, S]; None otherwise."""
+        if not self.pos_ptr:
+            return None
+        n = self.rows() if n_rows is None else n_rows
+        a = np.zeros((n, self.S), np.int32)
+        return native.d2h(self.h, a, self.pos_ptr, a.nbytes)
+
     def tensors(self, n_rows=None, device=None):
         """The planes as zero-copy torch tensors on the device, keyed as the
         reference's DataSet (input_ids, attention_mask, token_type_ids when the
@@ -95,6 +104,7 @@ class DeviceResult:
         for key, ptr, w, ts in (("input_ids", self.r.input_ids, S, "<i4"),
                                 ("attention_mask", self.r.attention_mask, S, "<i4"),
                                 ("token_type_ids", self.r.token_type_ids, S, "<i4"),
+                                ("position_ids", self.pos_ptr, S, "<i4"),  # packed clm rows only
                                 ("labels", self.r.labels_f32 or self.r.labels, LW, "<f4" if self.r.labels_f32 else "<i4")):
             if ptr and n > 0:
                 out[key] = torch.as_tensor(_CudaView(ptr, (n, w), ts, self.stream), device=dev)
@@ -144,7 +154,7 @@ class DeviceBatcher:
     def __init__(self, task=native.SDL_TASK_MLM, batch_size=256, sequence_length=512, mask_length=None,
                  mask_id=103, seed=0, device=0, tokenizer=native.BERT_PROXY_TOKENIZER, chunk=True, min_ids=None,
                  number_labels=9, avg_span_gap=16.0, avg_span_size=2.0, rng_mode=0, mask_policy=0,
-                 mask_per_mille=150):
+                 mask_per_mille=150, pack=0):
         L = native.load()
         c = native.default_config(task)
         c.batch_size, c.sequence_length = batch_size, sequence_length
@@ -153,6 +163,7 @@ class DeviceBatcher:
         c.number_labels = number_labels
         c.rng_mode = rng_mode
         c.mask_policy, c.mask_per_mille = mask_policy, mask_per_mille
+        c.pack = int(pack)
         c.avg_span_gap, c.avg_span_size = avg_span_gap, avg_span_size
         if min_ids is not None:
             c.min_ids = min_ids
@@ -187,7 +198,15 @@ class DeviceBatcher:
                                                       ctypes.c_void_p(offsets_ptr), n_records, first_record,
                                                       ctypes.c_void_p(stream or None), ctypes.byref(out)))
         return DeviceResult(self._h, out, n_records, self.cfg.sequence_length, self.cfg.batch_size, self.cfg.device,
-                            stream)
+                            stream, native.load().sdl_device_position_ids(self._h))
+
+    def flush_device(self, stream=0):
+        """Packed clm rows (pack=1): the carry as one last row (sdl_pack_flush_device) -- a result
+        of 0 or 1 rows in row 0 of the planes; the carry is empty afterwards."""
+        out = native.DeviceRows()
+        native.check(native.load().sdl_pack_flush_device(self._h, ctypes.c_void_p(stream or None), ctypes.byref(out)))
+        return DeviceResult(self._h, out, 0, self.cfg.sequence_length, self.cfg.batch_size, self.cfg.device, stream,
+                            native.load().sdl_device_position_ids(self._h))
 
     def process_labels(self, text_ptr, text_len, offsets_ptr, n_records, labels_ptr, label_offsets_ptr,
                        first_record=0, stream=0):

@@ -25,6 +25,7 @@ SDL_MASK_REFERENCE, SDL_MASK_BERT, SDL_MASK_BERT_WHOLE_WORD = 0, 1, 2
 EXPORTS = [
     "sdl_config_default", "sdl_batcher_create", "sdl_batcher_destroy", "sdl_batcher_push",
     "sdl_batcher_push_many", "sdl_batcher_next", "sdl_batcher_flush", "sdl_batch_release",
+    "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids",
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
     "sdl_gzip_inflate_device", "sdl_gzip_inflate_first_device", "sdl_gzip_split_members", "sdl_build_id",
@@ -39,7 +40,20 @@ class SDLError(RuntimeError):
         self.code = code
 
 
+class _PackWord(ctypes.Structure):
+    _fields_ = [("pack", ctypes.c_int32)]  # clm: 1 = documents concatenated and cut into full rows
+
+
+class _ConfigTail(ctypes.Union):
+    """The last four words of sdl_config: `pack`, then the header's reserved[3].  `reserved` stays
+    the four-word view callers of this module have always had (pack was carved out of its first
+    word, as mask_policy was carved out of the words before it): reserved[0] is pack."""
+    _anonymous_ = ("_w",)
+    _fields_ = [("_w", _PackWord), ("reserved", ctypes.c_int32 * 4)]
+
+
 class Config(ctypes.Structure):
+    _anonymous_ = ("_tail",)
     _fields_ = [
         ("task", ctypes.c_int32), ("batch_size", ctypes.c_int32), ("sequence_length", ctypes.c_int32),
         ("chunk", ctypes.c_int32), ("min_ids", ctypes.c_int32), ("mask_length", ctypes.c_int32),
@@ -48,7 +62,7 @@ class Config(ctypes.Structure):
         ("seed", ctypes.c_uint64), ("first_record", ctypes.c_uint64),
         ("device", ctypes.c_int32), ("rng_mode", ctypes.c_int32),
         ("mask_policy", ctypes.c_int32), ("mask_per_mille", ctypes.c_int32),  # SDL_MASK_*; policies 1 / 2
-        ("reserved", ctypes.c_int32 * 4),
+        ("_tail", _ConfigTail),  # pack, reserved
     ]
 
 
@@ -186,6 +200,12 @@ def load(path=LIB_PATH):
     L.sdl_process_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, ctypes.POINTER(DeviceRows)]
     L.sdl_process_device_labels.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, ctypes.POINTER(DeviceRows)]
     L.sdl_device_to_host.argtypes = [vp, vp, vp, sz, vp]
+    L.sdl_batch_position_ids.argtypes = [ctypes.POINTER(Batch)]
+    L.sdl_batch_position_ids.restype = ctypes.POINTER(ctypes.c_int32)
+    L.sdl_pack_flush_device.argtypes = [vp, vp, ctypes.POINTER(DeviceRows)]
+    L.sdl_pack_flush_device.restype = i64
+    L.sdl_device_position_ids.argtypes = [vp]
+    L.sdl_device_position_ids.restype = vp
     L.sdl_json_text_device.argtypes = [vp, vp, u64, vp, ctypes.POINTER(JsonText)]
     L.sdl_pickle_frames_device.argtypes = [vp, ctypes.POINTER(DeviceRows), u64, i64, vp, ctypes.POINTER(Frames)]
     L.sdl_json_to_frames.argtypes = [vp, vp, u64, u64, i64, FRAME_SINK, vp, ctypes.POINTER(JsonFramesStats)]
