@@ -197,6 +197,8 @@ hipError_t launch_gz_crc_fold(const uint32_t *crc, const uint32_t *shift, uint64
 int64_t scan_tmp_words(int64_t n);
 hipError_t launch_exclusive_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *tmp, hipStream_t st,
                                  const uint32_t *carry_in = nullptr);
+// the most elements the scan takes in one workgroup and one launch
+int64_t scan_small_max();
 
 // zstd.hip: Zstandard frames -> their bytes back to back (the provider's ZstdDecoder).  Per-frame
 // status (ZS_*, the codes of zstd_format.hpp); the output of frame f is [ooff[f], ooff[f + 1]).
@@ -278,10 +280,13 @@ struct SegSel {
     int last;
 };
 
-// per record: token offset, token count, rows it yields (gen_batcher.rs:69-94)
+// per record: token offset, token count, rows it yields (gen_batcher.rs:69-94).  tile_sums (one
+// segment only, records_tile_words(R) words): also the rows of every tile of records, the input
+// of launch_scan_rows_map.
+int64_t records_tile_words(int64_t R);
 hipError_t launch_records(const RowParams &P, const uint64_t *off, int64_t R, int64_t N, const uint32_t *chunk_off,
                           int64_t n_chunks, const uint32_t *rec_local, uint32_t *rec_tok, uint32_t *rec_cnt,
-                          uint32_t *rec_rows, SegSel sel, hipStream_t st);
+                          uint32_t *rec_rows, SegSel sel, hipStream_t st, uint32_t *tile_sums = nullptr);
 
 // Small pushes, no second round trip: global row g of the call goes to slot
 // base + g of the back batch (slots >= B: the next, pre-allocated one), rows
@@ -344,6 +349,10 @@ struct RowChunkIn {
 };
 hipError_t launch_row_map(const uint32_t *row_off, int64_t R, uint32_t *row_rec, SegSel sel, hipStream_t st,
                           const RowChunkIn *rc = nullptr);
+// One segment, R > 0: row_off[0..R] = the exclusive scan of rec_rows from launch_records' tile
+// sums, and the row map above, in one launch.
+hipError_t launch_scan_rows_map(const uint32_t *rec_rows, int64_t R, const uint32_t *tile_sums, uint32_t *row_off,
+                                uint32_t *row_rec, hipStream_t st, const RowChunkIn *rc = nullptr);
 
 // BertData::put_data + mask_batch for every row (models/bert_data.rs:40-89)
 // pipeline.hip: device rows -> finished batches in pinned host memory (the

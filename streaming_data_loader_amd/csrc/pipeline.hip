@@ -18,14 +18,22 @@
 namespace sdl {
 
 // ---------------------------------------------------------------------------
-// Exclusive scan (reduce -> scan of tile sums -> apply), u32.
+// Exclusive scan (reduce -> apply), u32.  The reduce leaves one sum per tile (and the carry
+// behind them); an apply block adds up the sums of the tiles before its own -- a few hundred
+// values at most for a call's chunks or records -- so no launch scans the tile sums in between.
 // ---------------------------------------------------------------------------
 constexpr int SCAN_NT = 256;
 constexpr int SCAN_PER = 8;
 constexpr int SCAN_TILE = SCAN_NT * SCAN_PER;
+// the most apply blocks: past it a block takes a run of consecutive tiles, so the sums read by
+// all blocks together stay linear in the tiles (SCAN_MAX_BLOCKS / 2 loads a tile)
+constexpr int64_t SCAN_MAX_BLOCKS = 1024;
 
+// sums[b] = the sum of tile b; sums[nb] = the carry (the scan's first value).  The carry may be
+// out[0] itself: it is read here, a launch before the apply rewrites it.
 __global__ __launch_bounds__(SCAN_NT) void k_scan_reduce(const uint32_t *__restrict__ in, int64_t n,
-                                                         uint32_t *__restrict__ sums) {
+                                                         uint32_t *__restrict__ sums, int64_t nb,
+                                                         const uint32_t *carry_in) {
     __shared__ uint32_t scratch[SCAN_NT / 64];
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_PER;
     uint32_t s = 0;
@@ -34,52 +42,47 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_reduce(const uint32_t *__restr
         if (base + k < n) s += in[base + k];
     uint32_t tot;
     block_excl_sum<SCAN_NT>(s, &tot, scratch);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+    if (threadIdx.x == 0) {
+        sums[blockIdx.x] = tot;
+        if (blockIdx.x == 0) sums[nb] = carry_in ? *carry_in : 0u;
+    }
 }
 
-__global__ __launch_bounds__(SCAN_NT) void k_scan_sums(uint32_t *__restrict__ sums, int64_t nb,
-                                                       const uint32_t *carry_in) {
+// The sum of sums[0, t_lo) over the block, the same in every thread (two barriers).
+__device__ __forceinline__ uint32_t block_sum_before(const uint32_t *__restrict__ sums, int64_t t_lo,
+                                                     uint32_t *scratch) {
+    uint32_t p = 0, tot;
+    for (int64_t i = threadIdx.x; i < t_lo; i += SCAN_NT) p += sums[i];
+    block_excl_sum<SCAN_NT>(p, &tot, scratch);
+    return tot;
+}
+
+// Block b scans tiles [b * tpb, (b + 1) * tpb) (tpb = 1 up to SCAN_MAX_BLOCKS tiles); the block
+// of the last tile writes out[n].
+__global__ __launch_bounds__(SCAN_NT) void k_scan_apply(const uint32_t *__restrict__ in, int64_t n,
+                                                        const uint32_t *__restrict__ sums, int64_t nb, int64_t tpb,
+                                                        uint32_t *__restrict__ out) {
     __shared__ uint32_t scratch[SCAN_NT / 64];
-    uint32_t carry = carry_in ? *carry_in : 0u;
-    for (int64_t t0 = 0; t0 < nb; t0 += SCAN_TILE) {
-        const int64_t base = t0 + (int64_t)threadIdx.x * SCAN_PER;
+    const int64_t t_lo = (int64_t)blockIdx.x * tpb, t_hi = t_lo + tpb < nb ? t_lo + tpb : nb;
+    uint32_t carry = block_sum_before(sums, t_lo, scratch) + sums[nb];
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t base = t * SCAN_TILE + (int64_t)threadIdx.x * SCAN_PER;
         uint32_t v[SCAN_PER], s = 0;
 #pragma unroll
         for (int k = 0; k < SCAN_PER; ++k) {
-            v[k] = base + k < nb ? sums[base + k] : 0u;
+            v[k] = base + k < n ? in[base + k] : 0u;
             s += v[k];
         }
         uint32_t tot;
         uint32_t ex = block_excl_sum<SCAN_NT>(s, &tot, scratch) + carry;
 #pragma unroll
         for (int k = 0; k < SCAN_PER; ++k) {
-            if (base + k < nb) sums[base + k] = ex;
+            if (base + k < n) out[base + k] = ex;
             ex += v[k];
         }
         carry += tot;
     }
-    if (threadIdx.x == 0) sums[nb] = carry;
-}
-
-__global__ __launch_bounds__(SCAN_NT) void k_scan_apply(const uint32_t *__restrict__ in, int64_t n,
-                                                        const uint32_t *__restrict__ sums, int64_t nb,
-                                                        uint32_t *__restrict__ out) {
-    __shared__ uint32_t scratch[SCAN_NT / 64];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_PER;
-    uint32_t v[SCAN_PER], s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; ++k) {
-        v[k] = base + k < n ? in[base + k] : 0u;
-        s += v[k];
-    }
-    uint32_t tot;
-    uint32_t ex = block_excl_sum<SCAN_NT>(s, &tot, scratch) + sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; ++k) {
-        if (base + k < n) out[base + k] = ex;
-        ex += v[k];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = sums[nb];
+    if (t_hi == nb && threadIdx.x == 0) out[n] = carry;
 }
 
 // n <= SCAN_SMALL: one workgroup, one launch (a per-record push scans a handful
@@ -118,11 +121,14 @@ hipError_t launch_exclusive_scan(const uint32_t *in, uint32_t *out, int64_t n, u
         return hipGetLastError();
     }
     const int64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, tmp);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_NT), 0, st, tmp, nb, carry_in);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, tmp, nb, out);
+    const int64_t tpb = (nb + SCAN_MAX_BLOCKS - 1) / SCAN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, tmp, nb, carry_in);
+    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)((nb + tpb - 1) / tpb)), dim3(SCAN_NT), 0, st, in, n, tmp, nb, tpb,
+                       out);
     return hipGetLastError();
 }
+
+int64_t scan_small_max() { return SCAN_SMALL; }
 
 // ---------------------------------------------------------------------------
 // Pipelined segments (kernels.hpp SegChunks): rb[k] = first record whose ids
@@ -207,10 +213,15 @@ __device__ __forceinline__ RowSpan row_span(const SegSel &s, const uint32_t *row
 // when given: two launches fewer per call.  And, for a small push, its H2D: the grid copies the
 // staged blob from mapped pinned memory (cn16 16-B units; the offsets are then read from there
 // too) -- no copy in the stream before it.
+// The three searches of a chunk run in LDS, over the run of offsets the block's 256 chunks can
+// touch (RANGES_CAP entries, 16 KB; the bench arena's blocks touch about 130).
+constexpr int RANGES_CAP = 2048;
 __global__ __launch_bounds__(256) void k_chunk_ranges(const uint64_t *__restrict__ off, int64_t R, int64_t n_chunks,
                                                       uint32_t *__restrict__ ranges, uint32_t *__restrict__ rb1,
                                                       uint32_t *__restrict__ zero1, const uint4 *__restrict__ csrc,
                                                       uint4 *__restrict__ cdst, int64_t cn16) {
+    __shared__ uint64_t s_off[RANGES_CAP];
+    __shared__ int64_t s_br[2];
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     for (int64_t x = c; x < cn16; x += (int64_t)gridDim.x * 256) cdst[x] = csrc[x];
     if (c == 0) {
@@ -220,9 +231,53 @@ __global__ __launch_bounds__(256) void k_chunk_ranges(const uint64_t *__restrict
         }
         if (zero1) *zero1 = 0u;
     }
+    const int64_t cA = (int64_t)blockIdx.x * 256;  // the block's chunks: [cA, cZ]
+    if (cA >= n_chunks) return;                     // (the whole block)
+    const int64_t cZ = cA + 255 < n_chunks ? cA + 255 : n_chunks - 1;
+    // Every target of the block lies in [xa, xz], so every answer in [lower(xa), lower(xz)]: the
+    // block's bracket, about 130 records at 2 KB a record.  Waves 0 and 1 find one end each, 64
+    // probes a step (three or four dependent loads, not seventeen).
+    const int64_t xa = cA * CHUNK - HALO_L, xz = cZ * CHUNK - HALO_L + WIN;
+    const int wid = (int)(threadIdx.x >> 6), lane = lane_id();
+    if (wid < 2) {
+        const int64_t x = wid == 0 ? xa : xz;
+        int64_t lo = 0, hi = R + 1;  // the answer is in [lo, hi]
+        while (lo < hi) {
+            const int64_t st = (hi - lo + 63) >> 6, m = lo + lane * st;
+            const bool below = m < hi && (int64_t)off[m] < x;  // (true for the first cnt lanes: off rises)
+            const int cnt = __popcll(__ballot(below));
+            if (cnt == 0) {
+                hi = lo;
+            } else {
+                const int64_t h = lo + cnt * st;
+                lo = lo + (cnt - 1) * st + 1;
+                hi = h < hi ? h : hi;
+            }
+        }
+        if (lane == 0) s_br[wid] = lo;
+    }
+    __syncthreads();
+    const int64_t b_lo = s_br[0], b_hi = s_br[1];
+    // offsets [b_lo, b_hi) in LDS when they fit (a search probes indices below its upper end
+    // only); a longer run -- more than RANGES_CAP records in the block's 256 KiB -- keeps the
+    // search of the whole array in global memory (the same for the whole block)
+    const bool fits = b_hi - b_lo <= RANGES_CAP;
+    if (fits) {
+        for (int64_t i = threadIdx.x; i < b_hi - b_lo; i += 256) s_off[i] = off[b_lo + i];
+        __syncthreads();
+    }
     if (c >= n_chunks) return;
     auto lower = [&](int64_t x) {  // first r in [0, R] with off[r] >= x (R+1 if none)
         int64_t lo = 0, hi = R + 1;
+        if (fits) {
+            lo = b_lo;
+            hi = b_hi;
+            while (lo < hi) {
+                const int64_t m = (lo + hi) >> 1;
+                if ((int64_t)s_off[m - b_lo] < x) lo = m + 1; else hi = m;
+            }
+            return lo;
+        }
         while (lo < hi) {
             const int64_t m = (lo + hi) >> 1;
             if ((int64_t)off[m] < x) lo = m + 1; else hi = m;
@@ -297,40 +352,115 @@ __global__ __launch_bounds__(256) void k_records(RowParams P, const uint64_t *__
         record_one(P, off, r, N, chunk_off, n_chunks, rec_local, rec_tok, rec_cnt, rec_rows);
 }
 
+// The same over every record of a call, a block taking whole tiles of REC_TILE records (however
+// the grid is capped), and tile_sums[t] = the rows of tile t's records: the row scan's reduce,
+// done where the values are made.
+constexpr int REC_TILE = 256;
+__global__ __launch_bounds__(REC_TILE) void k_records_tiles(RowParams P, const uint64_t *__restrict__ off, int64_t R,
+                                                            int64_t N, const uint32_t *__restrict__ chunk_off,
+                                                            int64_t n_chunks, const uint32_t *__restrict__ rec_local,
+                                                            uint32_t *__restrict__ rec_tok,
+                                                            uint32_t *__restrict__ rec_cnt,
+                                                            uint32_t *__restrict__ rec_rows,
+                                                            uint32_t *__restrict__ tile_sums) {
+    __shared__ uint32_t scratch[REC_TILE / 64];
+    const int64_t nt = (R + REC_TILE - 1) / REC_TILE;
+    for (int64_t t = blockIdx.x; t < nt; t += gridDim.x) {
+        const int64_t r = t * REC_TILE + threadIdx.x;
+        uint32_t rows = 0, tot;
+        if (r < R) rows = record_one(P, off, r, N, chunk_off, n_chunks, rec_local, rec_tok, rec_cnt, rec_rows);
+        block_excl_sum<REC_TILE>(rows, &tot, scratch);
+        if (threadIdx.x == 0) tile_sums[t] = tot;
+    }
+}
+
+int64_t records_tile_words(int64_t R) { return (R + REC_TILE - 1) / REC_TILE + 1; }
+
 hipError_t launch_records(const RowParams &P, const uint64_t *off, int64_t R, int64_t N, const uint32_t *chunk_off,
                           int64_t n_chunks, const uint32_t *rec_local, uint32_t *rec_tok, uint32_t *rec_cnt,
-                          uint32_t *rec_rows, SegSel sel, hipStream_t st) {
+                          uint32_t *rec_rows, SegSel sel, hipStream_t st, uint32_t *tile_sums) {
     if (R == 0) return hipSuccess;
     const int64_t want = (R + 255) / 256;
-    hipLaunchKernelGGL(k_records, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, P, off, R, N,
-                       chunk_off, n_chunks, rec_local, rec_tok, rec_cnt, rec_rows, sel);
+    const dim3 grid((unsigned)(want < 1024 ? want : 1024));
+    if (tile_sums)  // (one segment: every record of the call)
+        hipLaunchKernelGGL(k_records_tiles, grid, dim3(REC_TILE), 0, st, P, off, R, N, chunk_off, n_chunks, rec_local,
+                           rec_tok, rec_cnt, rec_rows, tile_sums);
+    else
+        hipLaunchKernelGGL(k_records, grid, dim3(256), 0, st, P, off, R, N, chunk_off, n_chunks, rec_local, rec_tok,
+                           rec_cnt, rec_rows, sel);
     return hipGetLastError();
 }
 
-// Row g -> its record (one thread per record writes its rows' entries).  RC: and the chunk whose
-// list holds the row's first id (TokSrc.row_chunk) -- the rows of a record start at rising id
-// indices, so each search starts at the previous row's chunk.
+// Row g -> its record (one thread per record writes its rows' entries, g0 <= g < g1).  RC: and the
+// chunk whose list holds the row's first id (TokSrc.row_chunk) -- the rows of a record start at
+// rising id indices, so each search starts at the previous row's chunk.
+template <bool RC>
+__device__ __forceinline__ void row_map_one(int64_t r, uint32_t g0, uint32_t g1, uint32_t *__restrict__ row_rec,
+                                            const RowChunkIn &rc) {
+    if constexpr (RC) {
+        if (g0 == g1) return;
+        ListBracket br = list_bracket(rc.off[r], rc.off[r + 1], rc.n_lists);
+        const uint32_t t0 = rc.rec_tok[r], cnt = rc.rec_cnt[r];
+        for (uint32_t g = g0; g < g1; ++g) {
+            row_rec[g] = (uint32_t)r;
+            const int64_t base = rc.chunk ? (int64_t)(g - g0) * rc.S : 0;
+            const int64_t rel0 = base > rc.n_pre ? base - rc.n_pre : 0;  // the row's first id of the record's
+            if (rel0 < (int64_t)cnt) br.lo = list_chunk_of(rc.chunk_off, br.lo, br.hi, t0 + (uint32_t)rel0);
+            rc.row_chunk[g] = (uint32_t)br.lo;
+        }
+    } else {
+        for (uint32_t g = g0; g < g1; ++g) row_rec[g] = (uint32_t)r;
+    }
+}
+
 template <bool RC>
 __global__ __launch_bounds__(256) void k_row_map(const uint32_t *__restrict__ row_off, uint32_t *__restrict__ row_rec,
                                                  SegSel sel, RowChunkIn rc) {
     const int64_t r_lo = sel.rb[sel.k], r_hi = sel.rb[sel.k + 1];
-    for (int64_t r = r_lo + (int64_t)blockIdx.x * 256 + threadIdx.x; r < r_hi; r += (int64_t)gridDim.x * 256) {
-        const uint32_t g0 = row_off[r], g1 = row_off[r + 1];
-        if constexpr (RC) {
-            if (g0 == g1) continue;
-            ListBracket br = list_bracket(rc.off[r], rc.off[r + 1], rc.n_lists);
-            const uint32_t t0 = rc.rec_tok[r], cnt = rc.rec_cnt[r];
-            for (uint32_t g = g0; g < g1; ++g) {
-                row_rec[g] = (uint32_t)r;
-                const int64_t base = rc.chunk ? (int64_t)(g - g0) * rc.S : 0;
-                const int64_t rel0 = base > rc.n_pre ? base - rc.n_pre : 0;  // the row's first id of the record's
-                if (rel0 < (int64_t)cnt) br.lo = list_chunk_of(rc.chunk_off, br.lo, br.hi, t0 + (uint32_t)rel0);
-                rc.row_chunk[g] = (uint32_t)br.lo;
-            }
-        } else {
-            for (uint32_t g = g0; g < g1; ++g) row_rec[g] = (uint32_t)r;
+    for (int64_t r = r_lo + (int64_t)blockIdx.x * 256 + threadIdx.x; r < r_hi; r += (int64_t)gridDim.x * 256)
+        row_map_one<RC>(r, row_off[r], row_off[r + 1], row_rec, rc);
+}
+
+// The row scan's apply over k_records_tiles' sums (as k_scan_apply: a block adds up the sums of
+// the tiles before its own) with the row map in it: the thread that turns rec_rows[r] into
+// row_off[r] holds the record's row range and writes its rows' entries.  Block b takes tiles
+// [b * tpb, (b + 1) * tpb); the block of the last tile writes row_off[R].
+template <bool RC>
+__global__ __launch_bounds__(REC_TILE) void k_scan_rows_map(const uint32_t *__restrict__ rec_rows, int64_t R,
+                                                            const uint32_t *__restrict__ tile_sums, int64_t nt,
+                                                            int64_t tpb, uint32_t *__restrict__ row_off,
+                                                            uint32_t *__restrict__ row_rec, RowChunkIn rc) {
+    static_assert(REC_TILE == SCAN_NT, "block_sum_before strides by SCAN_NT");
+    __shared__ uint32_t scratch[REC_TILE / 64];
+    const int64_t t_lo = (int64_t)blockIdx.x * tpb, t_hi = t_lo + tpb < nt ? t_lo + tpb : nt;
+    uint32_t carry = block_sum_before(tile_sums, t_lo, scratch);
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t r = t * REC_TILE + threadIdx.x;
+        const uint32_t v = r < R ? rec_rows[r] : 0u;
+        uint32_t tot;
+        const uint32_t g0 = block_excl_sum<REC_TILE>(v, &tot, scratch) + carry;
+        if (r < R) {
+            row_off[r] = g0;
+            row_map_one<RC>(r, g0, g0 + v, row_rec, rc);
         }
+        carry += tot;
     }
+    if (t_hi == nt && threadIdx.x == 0) row_off[R] = carry;
+}
+
+hipError_t launch_scan_rows_map(const uint32_t *rec_rows, int64_t R, const uint32_t *tile_sums, uint32_t *row_off,
+                                uint32_t *row_rec, hipStream_t st, const RowChunkIn *rc) {
+    if (R <= 0) return hipErrorInvalidValue;
+    const int64_t nt = (R + REC_TILE - 1) / REC_TILE;
+    const int64_t tpb = (nt + SCAN_MAX_BLOCKS - 1) / SCAN_MAX_BLOCKS;
+    const dim3 grid((unsigned)((nt + tpb - 1) / tpb));
+    if (rc)
+        hipLaunchKernelGGL(k_scan_rows_map<true>, grid, dim3(REC_TILE), 0, st, rec_rows, R, tile_sums, nt, tpb, row_off,
+                           row_rec, *rc);
+    else
+        hipLaunchKernelGGL(k_scan_rows_map<false>, grid, dim3(REC_TILE), 0, st, rec_rows, R, tile_sums, nt, tpb,
+                           row_off, row_rec, RowChunkIn{});
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

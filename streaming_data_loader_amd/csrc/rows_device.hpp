@@ -154,10 +154,11 @@ __device__ __forceinline__ void compact_small(const SmallDown &d, int64_t cb, co
 // ---------------------------------------------------------------------------
 // Per record: where its ids start, how many, and how many rows it yields.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void record_one(const RowParams &P, const uint64_t *__restrict__ off, int64_t r, int64_t N,
-                                           const uint32_t *__restrict__ chunk_off, int64_t n_chunks,
-                                           const uint32_t *__restrict__ rec_local, uint32_t *__restrict__ rec_tok,
-                                           uint32_t *__restrict__ rec_cnt, uint32_t *__restrict__ rec_rows) {
+// (returns the record's rows)
+__device__ __forceinline__ uint32_t record_one(const RowParams &P, const uint64_t *__restrict__ off, int64_t r, int64_t N,
+                                               const uint32_t *__restrict__ chunk_off, int64_t n_chunks,
+                                               const uint32_t *__restrict__ rec_local, uint32_t *__restrict__ rec_tok,
+                                               uint32_t *__restrict__ rec_cnt, uint32_t *__restrict__ rec_rows) {
     auto tok_off = [&](int64_t q) -> uint32_t {
         const int64_t p = (int64_t)off[q];
         // (chunk_off[n_chunks], the total, is final once the last segment is scanned:
@@ -172,6 +173,7 @@ __device__ __forceinline__ void record_one(const RowParams &P, const uint64_t *_
     rec_tok[r] = a;
     rec_cnt[r] = cnt;
     rec_rows[r] = rows;
+    return rows;
 }
 
 // ---------------------------------------------------------------------------

@@ -557,7 +557,7 @@ struct sdl_batcher {
         rec_cnt.ensure((size_t)R + 1);
         rec_rows.ensure((size_t)R + 1);
         row_off.ensure((size_t)R + 1);
-        scan_tmp.ensure((size_t)std::max(scan_tmp_words(n_chunks), scan_tmp_words(R)) + 1);
+        scan_tmp.ensure((size_t)std::max({scan_tmp_words(n_chunks), scan_tmp_words(R), records_tile_words(R)}) + 1);
         const size_t plane = (size_t)std::max<int64_t>(rows_cap, 1) * P.S;
         o_ids.ensure(plane);
         o_am.ensure(plane);
@@ -691,19 +691,28 @@ struct sdl_batcher {
                 HIP_TRY(launch_compact_tokens(tokc.p + ca * (STAGE / 2), chunk_cnt.p + ca, chunk_off.p + ca, cz - ca,
                                               tok_ids.p, nullptr, nullptr, nullptr, nullptr, s, nullptr, STAGE, true));
             if (!piped) mark(4);
+            // one segment past the one-workgroup scan: k_records leaves the row scan's tile sums
+            // (scan_tmp: the chunk scan before it on the stream is done with them) and one launch
+            // scans the rows and maps them, in place of reduce, sums, apply and k_row_map
+            const bool scan_map = !piped && !pack() && R > scan_small_max();
             HIP_TRY(launch_records(p, d_off, R, N, chunk_off.p, n_chunks, rec_local.p, rec_tok.p, rec_cnt.p, rec_rows.p,
-                                   sel, s));
+                                   sel, s, scan_map ? scan_tmp.p : nullptr));
             if (!piped) mark(5);
             if (pack()) {  // rec_tok / rec_cnt exist: the stream's rows instead of row scan, row map and k_rows
                 mark(6);
                 run_pack(R, rows_cap, s);
                 return;
             }
-            if (piped) HIP_TRY(launch_scan_range(rec_rows.p, row_off.p, seg_rb.p, k, s));
-            else HIP_TRY(launch_exclusive_scan(rec_rows.p, row_off.p, R, scan_tmp.p, s));
             // (segment k's rows read lists and offsets of chunks < cz only: all written by now)
             const RowChunkIn rc{row_chunk.p, rec_tok.p, rec_cnt.p, chunk_off.p, d_off, cz, P.S, P.n_pre, P.chunk};
-            HIP_TRY(launch_row_map(row_off.p, R, row_rec.p, sel, s, from_lists ? &rc : nullptr));
+            if (scan_map) {
+                HIP_TRY(launch_scan_rows_map(rec_rows.p, R, scan_tmp.p, row_off.p, row_rec.p, s,
+                                             from_lists ? &rc : nullptr));
+            } else {
+                if (piped) HIP_TRY(launch_scan_range(rec_rows.p, row_off.p, seg_rb.p, k, s));
+                else HIP_TRY(launch_exclusive_scan(rec_rows.p, row_off.p, R, scan_tmp.p, s));
+                HIP_TRY(launch_row_map(row_off.p, R, row_rec.p, sel, s, from_lists ? &rc : nullptr));
+            }
             }
             const TokSrc src = from_lists ? TokSrc{nullptr, lists, chunk_off.p, cz, row_chunk.p}
                                           : TokSrc{tok_ids.p, nullptr, nullptr, 0, nullptr};
