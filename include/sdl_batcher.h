@@ -60,8 +60,10 @@ enum {
 
 /* Mirrors TrainingConfig.batch + .dataset_config (rust/src/config.rs:64-72,
  * rust/src/batcher.rs:11-14, rust/src/datasets/dataset_config.rs:7-16) plus the
- * RNG seed that replaces the reference's unseedable thread_rng(). */
-typedef struct sdl_config {
+ * RNG seed that replaces the reference's unseedable thread_rng().  96 bytes; the last three words
+ * are a C11 anonymous union (reserved[3], kept for callers that zero it, and the span policy's two
+ * words over reserved[0] and reserved[1]). */
+struct sdl_config {
     int32_t task;            /* SDL_TASK_* */
     int32_t batch_size;      /* BatchConfig.batch_size */
     int32_t sequence_length; /* BatchConfig.sequence_length */
@@ -88,8 +90,30 @@ typedef struct sdl_config {
     int32_t pack;            /* CLM, byte-level BPE: 0 = GenTokenizer's rows (every record cut into its own
                                 rows); 1 = documents concatenated with the end-of-text id and the stream
                                 cut into full rows ("Packed rows" below).  Carved out of reserved[4] */
-    int32_t reserved[3];
-} sdl_config;
+    union {                  /* the last three words under two views: a zeroed config is the reference's */
+        int32_t reserved[3];
+        struct {
+            int32_t span_policy;          /* SDL_SPAN_*: what a span row does with its ids (DESIGN.md §3
+                                             "Span policies").  0 = the reference's rule */
+            int32_t span_noise_per_mille; /* policy 1: noise ids per 1000 ids of a row (T5: 150), 1..500;
+                                             sdl_config_default leaves it 0, the caller states it */
+            int32_t reserved_tail_;       /* must be 0 */
+        };
+    };
+};
+typedef struct sdl_config sdl_config;
+
+/* sdl_config.span_policy (task span, rng_mode 0).  Policy 1 is T5's random_spans_noise_mask: a row
+ * of n ids has t = min(max((n * span_noise_per_mille + 500) / 1000, 1), n - 1) noise ids in
+ * m = min(max(1, floor(t / avg_span_size + 0.5)), t, n - t) spans (avg_span_size is the mean noise
+ * span length, T5: 3.0; avg_span_gap is ignored; n < 2: t = m = 0), both cut by uniformly random
+ * compositions; input_ids holds each span's kept ids and its sentinel, labels each sentinel and
+ * its noise ids and a closing sentinel, attention_mask is 1 over the filled input positions only.
+ * sdl_batcher_create refuses a config whose full row needs more than S/4 labels or 100 sentinels. */
+enum {
+    SDL_SPAN_REFERENCE = 0, /* T5Data::put_data: gaps and sizes drawn pass by pass */
+    SDL_SPAN_T5 = 1         /* fixed noise density, fixed span count, uniform span boundaries */
+};
 
 /* sdl_config.mask_policy (MLM, rng_mode 0).  The two BERT policies never pick 0, mask_id or the
  * framing ids ([CLS], [SEP]); they pick k = min(mask_length, max(1, (l * mask_per_mille + 500) /

@@ -51,6 +51,11 @@ class Gpt:
 class Span:
     avg_span_gap: float = 16.0
     avg_span_size: float = 2.0
+    # sdl_config.span_policy / span_noise_per_mille (DESIGN.md §3 "Span policies"): 0 the
+    # reference's rule; 1 T5's span corruption -- noise_per_mille of a row's ids (T5: 150) in spans
+    # of mean length avg_span_size (T5: 3.0), avg_span_gap ignored
+    policy: int = 0
+    noise_per_mille: int = 0
 
 
 @dataclass
@@ -173,9 +178,10 @@ class DataSet:
 
 
 def _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode, mask_policy=None,
-                   mask_per_mille=None):
+                   mask_per_mille=None, span_policy=None, span_noise_per_mille=None):
     """sdl_config for a ModelType/DataSetConfig pair (config.rs:43-62) -> (config, batch kind).
-    mask_policy / mask_per_mille, when given, override the Mask config's."""
+    mask_policy / mask_per_mille and span_policy / span_noise_per_mille, when given, override the
+    Mask and Span configs'."""
     if isinstance(dataset_config, Mask):
         task, kind = native.SDL_TASK_MLM, "bert"
     elif isinstance(dataset_config, Gpt):
@@ -196,6 +202,7 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
         c.pack = 1 if dataset_config.pack else 0
     if isinstance(dataset_config, Span):
         c.avg_span_gap, c.avg_span_size = dataset_config.avg_span_gap, dataset_config.avg_span_size
+        c.span_policy, c.span_noise_per_mille = dataset_config.policy, dataset_config.noise_per_mille
     if isinstance(dataset_config, MultiLabel):
         c.number_labels = dataset_config.number_labels
     c.seed, c.device, c.first_record, c.rng_mode = seed, device, first_record, rng_mode
@@ -203,6 +210,10 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
         c.mask_policy = mask_policy
     if mask_per_mille is not None:
         c.mask_per_mille = mask_per_mille
+    if span_policy is not None:
+        c.span_policy = span_policy
+    if span_noise_per_mille is not None:
+        c.span_noise_per_mille = span_noise_per_mille
     return c, kind
 
 
@@ -290,10 +301,11 @@ class _NativeBatcher(Batcher):
     def __init__(self, model_type: ModelType, batch_config: BatchConfig, dataset_config: DataSetConfig,
                  tokenizer: TokenizerConfig, chunk: bool = True, seed: int = 0, device: int = 0,
                  first_record: int = 0, rng_mode: int = 0, mask_policy: Optional[int] = None,
-                 mask_per_mille: Optional[int] = None):
+                 mask_per_mille: Optional[int] = None, span_policy: Optional[int] = None,
+                 span_noise_per_mille: Optional[int] = None):
         L = native.load()
         c, self.kind = _native_config(batch_config, dataset_config, chunk, seed, device, first_record, rng_mode,
-                                      mask_policy, mask_per_mille)
+                                      mask_policy, mask_per_mille, span_policy, span_noise_per_mille)
         h = ctypes.c_void_p()
         native.check(L.sdl_batcher_create(ctypes.byref(c), tokenizer.path.encode(), native.DATA_DIR.encode(),
                                           ctypes.byref(h)))
@@ -515,10 +527,11 @@ class ShardedGenTokenizer:
 
     def __init__(self, model_type: ModelType, batch_config: BatchConfig, dataset_config: DataSetConfig,
                  tokenizer: TokenizerConfig, devices, chunk: bool = True, seed: int = 0, first_record: int = 0,
-                 rng_mode: int = 0, mask_policy: Optional[int] = None, mask_per_mille: Optional[int] = None):
+                 rng_mode: int = 0, mask_policy: Optional[int] = None, mask_per_mille: Optional[int] = None,
+                 span_policy: Optional[int] = None, span_noise_per_mille: Optional[int] = None):
         L = native.load()
         c, self.kind = _native_config(batch_config, dataset_config, chunk, seed, 0, first_record, rng_mode,
-                                      mask_policy, mask_per_mille)
+                                      mask_policy, mask_per_mille, span_policy, span_noise_per_mille)
         devs = (ctypes.c_int32 * len(devices))(*devices)
         m = ctypes.c_void_p()
         native.check(L.sdl_multi_create(ctypes.byref(c), tokenizer.path.encode(), native.DATA_DIR.encode(), devs,

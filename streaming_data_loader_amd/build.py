@@ -24,7 +24,7 @@ ARCH = os.environ.get("SDL_OFFLOAD_ARCH", "gfx950")
 SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
            "assets.cpp", "sdl_batcher.cpp"]
 HEADERS = ["common.hpp", "device_util.hpp", "kernels.hpp", "tok_device.hpp", "assets.hpp", "json.hpp", "unigram.hpp",
-           "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "pack_queue.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
+           "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "span_noise.hpp", "pack_queue.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(REPO, "include"), "-I", CSRC]
 
@@ -206,6 +206,14 @@ def build_ablations(levels=(3,)):
     record bits staged, nothing tokenized) -> var/abl3/libsdl_batcher.so (tools/pmc_calibration.py)."""
     return [build(defines=(f"SDL_ABLATE={n}",), lib=os.path.join(REPO, "var", f"abl{n}", "libsdl_batcher.so"),
                   build_dir=os.path.join(REPO, "build", f"abl{n}")) for n in levels]
+
+
+def build_span_ablations(levels=(1, 2)):
+    """Diagnostic builds of k_rows_span_t5 (SDL_SPAN_T5_ABLATE: 1 no Philox, 2 no selection either;
+    their rows are not the contract's) -> var/span_abl{n}/libsdl_batcher.so, for
+    SDL_LIB=... tools/span_policy_bench.py (where the policy's rows stage spends its time)."""
+    return [build(defines=(f"SDL_SPAN_T5_ABLATE={n}",), lib=os.path.join(REPO, "var", f"span_abl{n}", "libsdl_batcher.so"),
+                  build_dir=os.path.join(REPO, "build", f"span_abl{n}")) for n in levels]
 
 
 if __name__ == "__main__":

@@ -436,6 +436,17 @@ hipError_t launch_rows_span(const RowParams &P, const uint32_t *tok, const uint3
                             const uint32_t *row_off, const uint32_t *row_rec, SegSel sel, int64_t rows_cap,
                             RowOut out, uint32_t *err, hipStream_t st, const SpanPlan *plan = nullptr);
 
+// T5's span corruption (sdl_config.span_policy 1, DESIGN.md §3 "Span policies"): k_rows_span_t5's
+// own argument (a struct of its own, see MaskPolicy).  counts[n] = t | m << 16 for n in 0..S
+// (span_noise.hpp span_noise_table).  One launch writes the three planes of every row; *err counts
+// rows whose labels or sentinels would not fit (none, once sdl_batcher_create took the config).
+struct SpanNoise {
+    const uint32_t *counts;
+};
+hipError_t launch_rows_span_t5(const RowParams &P, const SpanNoise &sn, const uint32_t *tok, const uint32_t *rec_tok,
+                               const uint32_t *rec_cnt, const uint32_t *row_off, const uint32_t *row_rec, SegSel sel,
+                               int64_t rows_cap, RowOut out, uint32_t *err, hipStream_t st);
+
 hipError_t launch_single_labels(const uint32_t *labels, const uint64_t *label_off, const uint32_t *row_rec,
                                 const uint32_t *row_off, SegSel sel, int64_t rows_cap, int B, int32_t *out,
                                 uint32_t *err, hipStream_t st);

@@ -14,6 +14,7 @@
 #include "device_util.hpp"
 #include "kernels.hpp"
 #include "rows_device.hpp"
+#include "span_noise.hpp"
 
 namespace sdl {
 
@@ -1908,6 +1909,230 @@ hipError_t launch_rows_span(const RowParams &P, const uint32_t *tok, const uint3
     else
         hipLaunchKernelGGL(k_rows_span<0>, dim3(grid), dim3(256), dyn, st, P, tok, rec_tok, rec_cnt, row_off, row_rec,
                            sel, rows_cap, out, err, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// T5's span corruption (sdl_config.span_policy 1; DESIGN.md §3 "Span policies").  One wave per
+// row, one launch, no plan in global memory:
+//   1. the row's framed ids into LDS, (t, m) from the host's count table;
+//   2. twice -- the noise cuts over 1..t-1, the keep cuts over 1..u-1 -- lanes draw the Philox
+//      keys (one block is four positions' keys) into LDS, span_select_cuts (span_noise.hpp) finds
+//      the m - 1 smallest, and a ballot and prefix count per 64 positions compacts the cut flags
+//      into span starts in LDS.  Rows with m <= 1 draw nothing;
+//   3. lanes turn the starts into the plan entries k_span_write reads ({lp | a << 16,
+//      ip | b << 16}, in LDS), scatter each span's first input and label position into marks, and
+//      span_plane writes both planes position-parallel; attention_mask is 1 below u + m.
+// The keys' LDS words are reused for the marks.  The m = 0 row (n = 1) is one entry that keeps
+// its id.  A row whose labels or sentinels would not fit is counted in *err and left as a
+// padding row: sdl_batcher_create refuses every config that has one.
+// ---------------------------------------------------------------------------
+struct SpanWave {  // the wave, as span_noise.hpp asks for it
+    __device__ __forceinline__ uint32_t lane() const { return (uint32_t)lane_id(); }
+    __device__ __forceinline__ uint32_t lanes() const { return 64u; }
+    __device__ __forceinline__ uint32_t sum(uint32_t x) const {
+        return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_sum(x), 63);
+    }
+    __device__ __forceinline__ uint32_t min(uint32_t x) const {
+        DPP_SCAN_ID(x, min_u32r, 0xFFFFFFFFu);
+        return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+    }
+};
+
+constexpr int SPAN_T5_TAB = 128;  // plan entries and span starts a row holds in LDS (m <= 100)
+// Diagnostic builds only (build.py build_span_ablations): 1 = the keys from a
+// multiply in the place of Philox; 2 = also no selection and no compaction, spans of even lengths.
+// Their rows are not the contract's: they say where k_rows_span_t5's time goes.
+#ifndef SDL_SPAN_T5_ABLATE
+#define SDL_SPAN_T5_ABLATE 0
+#endif
+
+__global__ __launch_bounds__(256) void k_rows_span_t5(RowParams P, SpanNoise sn, const uint32_t *__restrict__ tok,
+                                                      const uint32_t *__restrict__ rec_tok,
+                                                      const uint32_t *__restrict__ rec_cnt,
+                                                      const uint32_t *__restrict__ row_off,
+                                                      const uint32_t *__restrict__ row_rec, SegSel sel,
+                                                      int64_t rows_cap, RowOut out, uint32_t *__restrict__ err) {
+    __shared__ int32_t s_extra[100];
+    __shared__ uint2 s_tab[4][SPAN_T5_TAB];
+    __shared__ uint16_t s_start[4][2][SPAN_T5_TAB];  // [0]: where each span's noise ids start, [1]: its kept ids
+    extern __shared__ int32_t s_dyn[];  // per wave: rid[S] | key[S], then mk[S] u16 | mk2[LW] u16 in the keys' place
+    const int lane = lane_id();
+    const int wid = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
+    if (threadIdx.x < 100) s_extra[threadIdx.x] = P.extra_ids[threadIdx.x];
+    __syncthreads();
+    const int S = P.S, LW = P.label_width;
+    int32_t *rid = s_dyn + (size_t)wid * 2 * S;
+    uint32_t *key = reinterpret_cast<uint32_t *>(rid + S);
+    uint16_t *mk = reinterpret_cast<uint16_t *>(key);
+    uint16_t *mk2 = mk + S;
+    uint2 *tl = s_tab[wid];
+    uint16_t *nb = s_start[wid][0], *ka = s_start[wid][1];
+    const RowSpan rs = row_span(sel, row_off, P.B, rows_cap);
+    const int64_t G = rs.g_real;
+    const SpanWave wv{};
+    auto extra = [&](uint32_t q) -> int32_t { return s_extra[q < 100u ? q : 99u]; };
+    auto fence = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    };
+    for (int64_t g = rs.g_lo + (int64_t)blockIdx.x * nw + wid; g < rs.g_end; g += (int64_t)gridDim.x * nw) {
+        int32_t *ids_o = out.input_ids + g * S;
+        int32_t *am_o = out.attention_mask + g * S;
+        int32_t *lb_o = out.labels + g * (int64_t)LW;
+        auto pad_row = [&] {  // T5Data::new's values
+            for (int j = lane; j < S; j += 64) {
+                st_nt(ids_o + j, 0);
+                st_nt(am_o + j, 1);
+            }
+            for (int j = lane; j < LW; j += 64) st_nt(lb_o + j, -100);
+        };
+        if (g >= G) {
+            pad_row();
+            continue;
+        }
+        const int64_t r = row_rec[g];
+        const uint32_t k = (uint32_t)(g - row_off[r]);
+        const uint32_t cnt = rec_cnt[r];
+        const uint32_t t0 = rec_tok[r];
+        const int64_t nf = (int64_t)cnt + P.n_pre + P.n_post;
+        const int64_t base = P.chunk ? (int64_t)k * S : 0;
+        const int n = (int)((nf - base) < S ? (nf - base) : S);
+        const uint32_t tm = n > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)sn.counts[n]) : 0u;
+        const int t = (int)(tm & 0xFFFFu), m = (int)(tm >> 16), u = n - t;
+        if (n <= 0 || m + 1 > SPAN_MAX_SENTINELS || t + m + 1 > LW) {  // (a row always holds >= 1 id)
+            pad_row();
+            if (lane == 0 && n > 0) atomicAdd(err, 1u);
+            continue;
+        }
+        auto fid = [&](int j) -> int32_t {  // framed id j of this chunk
+            const int64_t f = base + j;
+            if (f < P.n_pre) return frame_id(P.pre, (int)f);
+            if (f < P.n_pre + (int64_t)cnt) return (int32_t)tok[t0 + (f - P.n_pre)];
+            return frame_id(P.post, (int)(f - P.n_pre - cnt));
+        };
+        for (int j0 = 0; j0 < n; j0 += 64 * 8) {  // every load in flight together
+            int32_t v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int j = j0 + 64 * q + lane;
+                v[q] = j < n ? fid(j) : 0;
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int j = j0 + 64 * q + lane;
+                if (j < n) rid[j] = v[q];
+            }
+        }
+        if (lane == 0) {
+            nb[0] = 0;
+            ka[0] = 0;
+        }
+        if (SDL_SPAN_T5_ABLATE >= 2) {
+            for (int s = lane; s < m; s += 64) {
+                nb[s] = (uint16_t)((int64_t)s * t / m);
+                ka[s] = (uint16_t)((int64_t)s * u / m);
+            }
+            fence();
+        } else if (m > 1) {
+            const uint64_t rec = P.first_record + (uint64_t)r;
+#pragma unroll 1
+            for (int dom = 0; dom < 2; ++dom) {
+                const uint32_t nk = (uint32_t)(dom ? u : t) - 1u;  // cut candidates i = 1..nk, key[i - 1]
+                const uint32_t D = dom ? SPAN_KEEP_DOMAIN : SPAN_NOISE_DOMAIN;
+                uint16_t *st = dom ? ka : nb;
+                for (uint32_t q = (uint32_t)lane; 4u * q <= nk; q += 64u) {
+#if SDL_SPAN_T5_ABLATE >= 1
+                    const uint32_t h = (4u * q + (k | D) + (uint32_t)rec) * 0x9E3779B1u;
+                    const uint4 c = make_uint4(h, h + 0x9E3779B1u, h + 2u * 0x9E3779B1u, h + 3u * 0x9E3779B1u);
+#else
+                    const uint4 c = philox4x32_10(make_uint4(q, k | D, (uint32_t)rec, (uint32_t)(rec >> 32)),
+                                                  (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+#endif
+                    const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                    for (uint32_t e = 0; e < 4; ++e) {
+                        const uint32_t i = 4u * q + e;
+                        if (i >= 1u && i <= nk) key[i - 1u] = w[e];
+                    }
+                }
+                fence();
+                const SpanSel ss = span_select_cuts(key, nk, (uint32_t)m - 1u, wv);
+                uint32_t rank = 1;  // span 0 starts at 0
+                for (uint32_t b0 = 0; b0 < nk; b0 += 64u) {
+                    const uint32_t j = b0 + (uint32_t)lane;
+                    const bool f = j < nk && span_selected(ss, key[j], j);
+                    const uint64_t bal = __ballot(f);
+                    const uint32_t at = rank + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                    if (f && at < (uint32_t)SPAN_T5_TAB) st[at] = (uint16_t)(j + 1u);
+                    rank += (uint32_t)__popcll(bal);
+                }
+                fence();  // (the next keys, or the marks, overwrite these)
+            }
+        }
+        const int np = m > 0 ? m : 1;
+        for (int s = lane; s < np; s += 64) {
+            if (m == 0) {
+                tl[0] = make_uint2(0u | 1u << 16, 0u);  // the row's one id, kept; no span
+            } else {
+                const uint32_t A = ka[s], a = (s + 1 < m ? (uint32_t)ka[s + 1] : (uint32_t)u) - A;
+                const uint32_t Bn = nb[s], b = (s + 1 < m ? (uint32_t)nb[s + 1] : (uint32_t)t) - Bn;
+                const SpanEntry e = span_plan_entry((uint32_t)s, A, a, Bn, b);
+                tl[s] = make_uint2(e.x, e.y);
+            }
+        }
+        for (int j = 2 * lane; j < S + LW; j += 128) *reinterpret_cast<uint32_t *>(mk + j) = 0u;
+        fence();
+        for (int p = lane; p < np; p += 64) {
+            const uint2 e = tl[p];
+            const int lp = (int)(e.x & 0xFFFFu), ip = (int)(e.y & 0xFFFFu);
+            const int ap = ip - lp + 2 * p;
+            if (lp < S) mk[lp] = (uint16_t)p;
+            if (m > 0 && ap < LW) mk2[ap] = (uint16_t)p;
+        }
+        fence();
+        const int L = u + m;
+        span_plane(
+            ids_o, S, L, mk,
+            [&](int q, uint32_t o) -> int32_t {
+                const uint2 e = tl[o];
+                const int off = q - (int)(e.x & 0xFFFFu), ge = (int)(e.x >> 16);
+                return off < ge ? rid[(int)(e.y & 0xFFFFu) + off] : extra(o);
+            },
+            [&](int) -> int32_t { return 0; });
+        for (int j = lane; j < S; j += 64) st_nt(am_o + j, j < L ? 1 : 0);
+        const int ap_end = t + m;
+        const int32_t fin = extra((uint32_t)m);  // the closing sentinel
+        span_plane(
+            lb_o, LW, ap_end, mk2,
+            [&](int q, uint32_t o) -> int32_t {
+                const uint2 e = tl[o];
+                const int lp = (int)(e.x & 0xFFFFu), ge = (int)(e.x >> 16), ip = (int)(e.y & 0xFFFFu);
+                const int off = q - (ip - lp + 2 * (int)o);
+                return off == 0 ? extra(o) : rid[ip + ge + off - 1];
+            },
+            [&](int q) -> int32_t { return q == ap_end ? fin : -100; });
+        fence();  // (the next row rewrites rid, the plan and the marks)
+    }
+}
+
+hipError_t launch_rows_span_t5(const RowParams &P, const SpanNoise &sn, const uint32_t *tok, const uint32_t *rec_tok,
+                               const uint32_t *rec_cnt, const uint32_t *row_off, const uint32_t *row_rec, SegSel sel,
+                               int64_t rows_cap, RowOut out, uint32_t *err, hipStream_t st) {
+    if (rows_cap == 0) return hipSuccess;
+    // 8 S bytes of LDS a wave: four waves a block up to S = 1792, two beyond
+    if (!sn.counts || P.S < 1 || P.S > 3584 || P.rng_mode != 0) return hipErrorInvalidValue;
+    if (sel.k == 0) {  // the error count covers the whole call
+        hipError_t e = hipMemsetAsync(err, 0, sizeof(uint32_t), st);
+        if (e != hipSuccess) return e;
+    }
+    const int waves = 32 * P.S <= 56 * 1024 ? 4 : 2;
+    const int64_t want = (rows_cap + waves - 1) / waves;
+    const unsigned grid = (unsigned)(want < SPAN_GRID_CAP ? want : SPAN_GRID_CAP);
+    const size_t dyn = (size_t)waves * 2 * P.S * sizeof(int32_t);
+    hipLaunchKernelGGL(k_rows_span_t5, dim3(grid), dim3(64 * waves), dyn, st, P, sn, tok, rec_tok, rec_cnt, row_off,
+                       row_rec, sel, rows_cap, out, err);
     return hipGetLastError();
 }
 

@@ -30,6 +30,7 @@
 #include "assets.hpp"
 #include "kernels.hpp"
 #include "pack_queue.hpp"
+#include "span_noise.hpp"
 
 using namespace sdl;
 
@@ -278,6 +279,8 @@ struct sdl_batcher {
     DevBuf<uint32_t> d_trie;
     DevBuf<int32_t> d_extra;
     DevBuf<double> d_zig;  // span rng_mode 1: ZIG_NORM_X then ZIG_NORM_F (257 each)
+    DevBuf<uint32_t> d_span_counts;  // span policy 1: t | m << 16 for every n in 0..S (span_noise_table)
+    SpanNoise snoise{};              // ... as k_rows_span_t5 takes it; counts null = the reference's rule
 
     // per-call workspace
     DevBuf<uint32_t> row_chunk;  // row -> the chunk of its first id (rows read from the chunk lists)
@@ -717,7 +720,11 @@ struct sdl_batcher {
             const TokSrc src = from_lists ? TokSrc{nullptr, lists, chunk_off.p, cz, row_chunk.p}
                                           : TokSrc{tok_ids.p, nullptr, nullptr, 0, nullptr};
             if (!piped) mark(6);
-            if (span()) {
+            if (span() && snoise.counts) {  // (SDL_SPAN_TWO_PHASE has no effect: one kernel plans and writes)
+                span_err.ensure(1);
+                HIP_TRY(launch_rows_span_t5(p, snoise, tok_ids.p, rec_tok.p, rec_cnt.p, row_off.p, row_rec.p, sel,
+                                            rows_cap, out, span_err.p, s));
+            } else if (span()) {
                 span_err.ensure(1);
                 SpanPlan pl{};
                 const bool two_phase = span_two_phase;
@@ -1183,6 +1190,29 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
     }
     if (cfg->pack != 0 && cfg->pack != 1) return fail(SDL_ERR_ARG, "pack must be 0 (off) or 1 (packed rows)");
     if (cfg->pack == 1 && cfg->task != SDL_TASK_CLM) return fail(SDL_ERR_ARG, "pack = 1 applies to the CLM task only");
+    if (cfg->span_policy < SDL_SPAN_REFERENCE || cfg->span_policy > SDL_SPAN_T5)
+        return fail(SDL_ERR_ARG, "span_policy must be 0 (reference) or 1 (T5)");
+    if (cfg->span_policy == SDL_SPAN_T5) {
+        if (cfg->task != SDL_TASK_SPAN) return fail(SDL_ERR_ARG, "span_policy 1 applies to the span task only");
+        if (cfg->span_noise_per_mille < 1 || cfg->span_noise_per_mille > 500)
+            return fail(SDL_ERR_ARG, "span_noise_per_mille must be in [1, 500] under span_policy 1");
+        if (!std::isfinite(cfg->avg_span_size) || cfg->avg_span_size < 1.0)
+            return fail(SDL_ERR_ARG, "span_policy 1 reads avg_span_size as the mean noise span length: finite and >= 1.0");
+        if (cfg->rng_mode == 1)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "span_policy 1 needs rng_mode 0: the reference's own draws define no such policy");
+        // the full row is the worst case: t, m and t + m never decrease with n
+        int t = 0, m = 0;
+        const int S = cfg->sequence_length, LW = S / 4;
+        span_noise_counts(S, cfg->span_noise_per_mille, cfg->avg_span_size, &t, &m);
+        if (t + m + 1 > LW || m + 1 > SPAN_MAX_SENTINELS)
+            return fail(SDL_ERR_ARG,
+                        "span_policy 1: a full row of " + std::to_string(S) + " ids has " + std::to_string(t) +
+                            " noise ids in " + std::to_string(m) + " spans and needs " + std::to_string(t + m + 1) +
+                            " labels and " + std::to_string(m + 1) + " sentinels; the row holds " +
+                            std::to_string(LW) + " labels (S/4) and the vocabulary " +
+                            std::to_string(SPAN_MAX_SENTINELS) + " sentinels: lower span_noise_per_mille or raise avg_span_size");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(SDL_ERR_NODEV, "no HIP device visible: the Batcher runs only on the GPU (no CPU fallback)");
@@ -1386,6 +1416,13 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
                 HIP_TRY(hipMemcpy(h->d_zig.p, zt.data(), zt.size() * 8, hipMemcpyHostToDevice));
                 P.zig_x = h->d_zig.p;
                 P.zig_f = h->d_zig.p + 257;
+            }
+            if (cfg->span_policy == SDL_SPAN_T5) {  // the counts' one double step stays on the host
+                std::vector<uint32_t> tab((size_t)cfg->sequence_length + 1);
+                span_noise_table(cfg->sequence_length, cfg->span_noise_per_mille, cfg->avg_span_size, tab.data());
+                h->d_span_counts.ensure(tab.size());
+                HIP_TRY(hipMemcpy(h->d_span_counts.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+                h->snoise.counts = h->d_span_counts.p;
             }
         }
         if (cfg->task == SDL_TASK_MULTI_LABEL || cfg->task == SDL_TASK_SINGLE_CLASS) {  // SimpleBatcher: one row per record, no filter

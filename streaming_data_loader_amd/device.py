@@ -154,7 +154,7 @@ class DeviceBatcher:
     def __init__(self, task=native.SDL_TASK_MLM, batch_size=256, sequence_length=512, mask_length=None,
                  mask_id=103, seed=0, device=0, tokenizer=native.BERT_PROXY_TOKENIZER, chunk=True, min_ids=None,
                  number_labels=9, avg_span_gap=16.0, avg_span_size=2.0, rng_mode=0, mask_policy=0,
-                 mask_per_mille=150, pack=0):
+                 mask_per_mille=150, pack=0, span_policy=0, span_noise_per_mille=0):
         L = native.load()
         c = native.default_config(task)
         c.batch_size, c.sequence_length = batch_size, sequence_length
@@ -164,6 +164,7 @@ class DeviceBatcher:
         c.rng_mode = rng_mode
         c.mask_policy, c.mask_per_mille = mask_policy, mask_per_mille
         c.pack = int(pack)
+        c.span_policy, c.span_noise_per_mille = span_policy, span_noise_per_mille
         c.avg_span_gap, c.avg_span_size = avg_span_gap, avg_span_size
         if min_ids is not None:
             c.min_ids = min_ids

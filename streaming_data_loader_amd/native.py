@@ -20,6 +20,8 @@ T5_PROXY_TOKENIZER = os.path.join(ASSETS, "t5_proxy", "tokenizer.json")
 SDL_TASK_MLM, SDL_TASK_CLM, SDL_TASK_SPAN, SDL_TASK_MULTI_LABEL, SDL_TASK_SINGLE_CLASS = 0, 1, 2, 3, 4
 # sdl_config.mask_policy: the reference's rule, BERT 80/10/10 by token, ... by whole word
 SDL_MASK_REFERENCE, SDL_MASK_BERT, SDL_MASK_BERT_WHOLE_WORD = 0, 1, 2
+# sdl_config.span_policy: the reference's rule, T5's random_spans_noise_mask
+SDL_SPAN_REFERENCE, SDL_SPAN_T5 = 0, 1
 
 # every symbol include/sdl_batcher.h declares
 EXPORTS = [
@@ -41,13 +43,17 @@ class SDLError(RuntimeError):
 
 
 class _PackWord(ctypes.Structure):
-    _fields_ = [("pack", ctypes.c_int32)]  # clm: 1 = documents concatenated and cut into full rows
+    _fields_ = [("pack", ctypes.c_int32),  # clm: 1 = documents concatenated and cut into full rows
+                # span: SDL_SPAN_*; policy 1: noise ids per 1000 ids of a row (the header's reserved[0], [1])
+                ("span_policy", ctypes.c_int32), ("span_noise_per_mille", ctypes.c_int32)]
 
 
 class _ConfigTail(ctypes.Union):
-    """The last four words of sdl_config: `pack`, then the header's reserved[3].  `reserved` stays
-    the four-word view callers of this module have always had (pack was carved out of its first
-    word, as mask_policy was carved out of the words before it): reserved[0] is pack."""
+    """The last four words of sdl_config: `pack`, then the header's reserved[3] with span_policy
+    and span_noise_per_mille over its first two.  `reserved` stays the four-word view callers of
+    this module have always had (pack was carved out of its first word, as mask_policy was carved
+    out of the words before it): reserved[0] is pack, reserved[1] span_policy, reserved[2]
+    span_noise_per_mille."""
     _anonymous_ = ("_w",)
     _fields_ = [("_w", _PackWord), ("reserved", ctypes.c_int32 * 4)]
 
@@ -62,7 +68,7 @@ class Config(ctypes.Structure):
         ("seed", ctypes.c_uint64), ("first_record", ctypes.c_uint64),
         ("device", ctypes.c_int32), ("rng_mode", ctypes.c_int32),
         ("mask_policy", ctypes.c_int32), ("mask_per_mille", ctypes.c_int32),  # SDL_MASK_*; policies 1 / 2
-        ("_tail", _ConfigTail),  # pack, reserved
+        ("_tail", _ConfigTail),  # pack, span_policy, span_noise_per_mille, reserved
     ]
 
 

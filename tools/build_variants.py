@@ -24,6 +24,9 @@ DIAG_MACROS = {
     # inflate output batch bytes (tests/test_inflate_fuzz.py builds 256 with the next one)
     "SDL_GZ_OBUF": "inflate output batch bytes",
     "SDL_GZ_ALLOW_SMALL_OBUF": "lift the OBUF >= 512 static_assert (the no-progress exit test)",
+    # span policy 1: 1 = keys without Philox, 2 = also no selection and no compaction (rows not
+    # the contract's): where k_rows_span_t5's time goes (build.build_span_ablations, var/span_abl{1,2})
+    "SDL_SPAN_T5_ABLATE": "k_rows_span_t5 without its keys / its selections",
 }
 
 
