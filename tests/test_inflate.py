@@ -426,7 +426,7 @@ def big_lines(records, mib, seed=0):
 
 def chunked_cases(records):
     """(name, member, expected bytes): members of >= 1 MiB compressed take the
-    chunked path (GZ_SPLIT_MIN in sdl_batcher.cpp)."""
+    chunked path (GZ_SPLIT_MIN in provider_gzip.cpp)."""
     rng = random.Random(3)
     lines = big_lines(records, 8)
     noise = bytes(rng.randrange(256) for _ in range(1_200_000))
