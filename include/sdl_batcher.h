@@ -32,8 +32,8 @@
 extern "C" {
 #endif
 
-/* 9 still: sdl_zstd_split_frames and sdl_zstd_inflate_device were added without changing any
- * existing call or struct (an additive change keeps the version). */
+/* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device and the three sentence-pair calls were
+ * added without changing any existing call or struct (an additive change keeps the version). */
 #define SDL_ABI_VERSION 9
 
 enum {
@@ -97,7 +97,9 @@ struct sdl_config {
                                              "Span policies").  0 = the reference's rule */
             int32_t span_noise_per_mille; /* policy 1: noise ids per 1000 ids of a row (T5: 150), 1..500;
                                              sdl_config_default leaves it 0, the caller states it */
-            int32_t reserved_tail_;       /* must be 0 */
+            int32_t pair;                 /* single-class / multi-label, WordPiece: 0 = one text per record;
+                                             1 = two texts per example in one [CLS] A [SEP] B [SEP] row
+                                             ("Sentence pairs" below).  Other values are refused */
         };
     };
 };
@@ -173,6 +175,27 @@ typedef struct sdl_batcher sdl_batcher;
  * are not the rows one handle gives over the whole stream.  sdl_json_to_frames returns
  * SDL_ERR_UNSUPPORTED; sdl_pickle_frames_device frames a packed call's three reference keys. */
 
+/* ---- Sentence pairs (sdl_config.pair = 1; tasks single-class and multi-label, WordPiece) ----
+ * No counterpart in the reference (SimpleData.alt_text is tokenized and dropped, dataset.rs:47):
+ * what BERT-style classifiers are fine-tuned on (MNLI, QQP, QNLI, MRPC).  Example r is two texts
+ * A_r, B_r with tokenizer ids a, b (n_a, n_b of them, no special tokens).  With M = S - 3 the kept
+ * lengths (k_a, k_b) are those of tokenizers' longest_first truncation (right, stride 0):
+ *     n_a + n_b <= M: (n_a, n_b);  else lo = min, hi = max of the two,
+ *     hi = lo > M ? lo : max(lo, M - lo);  lo + hi > M: lo = M / 2, hi = M / 2 + M % 2;
+ *     (k_a, k_b) = n_a <= n_b ? (lo, hi) : (hi, lo)          (a tie: B gets the odd id)
+ * and the one row of the pair is
+ *     input_ids       [CLS] a[0..k_a) [SEP] b[0..k_b) [SEP] 0 ...
+ *     token_type_ids    0       0       0       1       1   0 ...
+ *     attention_mask    1       1       1       1       1   0 ...      (the plain orientation)
+ * -- what tokenizers' encode(A, B) gives under BertProcessing, truncated and padded to S.  An empty
+ * A or B is legal; there is no min_ids filter and no chunking: exactly one row per pair.  Labels
+ * are the task's, one set per pair.  Rows from *d_rows to the next multiple of B hold the unpaired
+ * task's initial values.  sequence_length >= 3.  A pair handle takes sdl_process_device_pairs,
+ * sdl_batcher_push_pair and sdl_batcher_push_many_pairs (sdl_batcher_next / _flush /
+ * sdl_pickle_frames_device as they are); the unpaired calls return SDL_ERR_STATE on it and the
+ * pair calls SDL_ERR_STATE on a handle with pair = 0.  sdl_json_to_frames and sdl_multi_create
+ * return SDL_ERR_UNSUPPORTED. */
+
 /* Defaults of the reference masking cases (masking_cases.rs:38-94) for `task`:
  * B=4096 S=128 chunk=1 min_ids=64 mask 15%/103, span 16.0/2.0, 9 labels. */
 void sdl_config_default(sdl_config *cfg, int32_t task);
@@ -203,6 +226,15 @@ int sdl_batcher_push_many(sdl_batcher *h, const uint8_t *arena, const uint64_t *
                           size_t *n_emitted);
 /* Pops the next batch queued by sdl_batcher_push_many: 1 = *out filled, 0 = none. */
 int sdl_batcher_next(sdl_batcher *h, sdl_batch *out);
+/* pair = 1: create_sync_batch for one example of two texts (either may be empty); labels as
+ * sdl_batcher_push.  Returns 1 and fills *out when this call emits a batch (every B-th pair). */
+int sdl_batcher_push_pair(sdl_batcher *h, const uint8_t *a, size_t len_a, const uint8_t *b, size_t len_b,
+                          const uint32_t *labels, size_t n_labels, sdl_batch *out);
+/* pair = 1: sdl_batcher_push_many over n_pairs examples: A_r is text range 2r and B_r range 2r+1
+ * of `arena` (2 * n_pairs + 1 offsets); pair r's labels are labels[label_offsets[r] ..
+ * label_offsets[r+1]) (n_pairs + 1 label offsets). */
+int sdl_batcher_push_many_pairs(sdl_batcher *h, const uint8_t *arena, const uint64_t *offsets, size_t n_pairs,
+                                const uint32_t *labels, const uint64_t *label_offsets, size_t *n_emitted);
 /* Batcher::get_working_batch() (gen_batcher.rs:96-98): pops the front batch
  * (possibly partial, possibly empty).  1 = *out filled, 0 = none left. */
 int sdl_batcher_flush(sdl_batcher *h, sdl_batch *out);
@@ -264,6 +296,15 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
                               const uint64_t *d_offsets, uint64_t n_records, const uint32_t *d_labels,
                               const uint64_t *d_label_offsets, uint64_t first_record, void *stream,
                               sdl_device_rows *out);
+
+/* pair = 1: sdl_process_device_labels over n_pairs examples of two texts: A_r is text range 2r
+ * and B_r range 2r+1 of the arena (d_offsets: 2 * n_pairs + 1 entries), so the tokenizer runs once
+ * over 2 * n_pairs records.  *d_rows = n_pairs; d_record_rows has n_pairs entries, each 1;
+ * d_tokens counts the ids of both sides before truncation; d_label_offsets has n_pairs + 1
+ * entries; the label index of pair r is first_record + r. */
+int sdl_process_device_pairs(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len, const uint64_t *d_offsets,
+                             uint64_t n_pairs, const uint32_t *d_labels, const uint64_t *d_label_offsets,
+                             uint64_t first_record, void *stream, sdl_device_rows *out);
 
 /* ---- Provider step: the JsonText filter on the device ----------------------
  * SourceFilter::JsonText over inflated JSON lines (gzip_file_provider.rs:30-50

@@ -83,29 +83,75 @@ def _int_offsets(buf, offset, n, width):
     return np.frombuffer(buf, dt, count=offset + n + 1, offset=0)[offset:offset + n + 1]
 
 
-def arena_from_batch(batch, text_col="sentence", label_col="labels") -> ArrowArena:
-    """One record batch -> text arena + offsets + label arrays, read straight
-    from the Arrow buffers (nulls are taken as empty text / no labels)."""
+def _utf8_column(batch, name):
+    """A utf8 column's value bytes (a view of the Arrow buffer, or an empty array), each row's
+    start in them and its length (int64; a null row has length 0)."""
     pa = _pa()
-    t = batch.column(batch.schema.get_field_index(text_col))
+    t = batch.column(batch.schema.get_field_index(name))
     if t.type not in (pa.utf8(), pa.large_utf8()):
-        raise TypeError(f"{text_col} must be utf8, got {t.type}")
+        raise TypeError(f"{name} must be utf8, got {t.type}")
     n = len(t)
     w = 8 if t.type == pa.large_utf8() else 4
     _, obuf, vbuf = t.buffers()
     o = _int_offsets(obuf, t.offset, n, w).astype(np.int64)
+    lens = np.diff(o)
     if t.null_count:
-        valid = np.asarray(t.is_valid())
-        lens = np.where(valid, np.diff(o), 0)
-        starts = o[:-1]
-        pieces = [np.frombuffer(vbuf, np.uint8, count=int(l), offset=int(s)) for s, l in zip(starts, lens)]
-        body = np.concatenate(pieces) if pieces else np.zeros(0, np.uint8)
+        lens = np.where(np.asarray(t.is_valid()), lens, 0)
+    values = np.frombuffer(vbuf, np.uint8) if vbuf is not None and vbuf.size else np.zeros(0, np.uint8)
+    return values, o[:-1], lens
+
+
+_GATHER_BLOCK = 4 << 20  # text bytes a gather step moves: bounds the index temporaries (about 40 B a byte)
+
+
+def _interleave(cols):
+    """Rows of several utf8 columns laid out row by row (A_0 B_0 A_1 B_1 ...), gathered from each
+    column's value bytes in place (a sliced batch's buffers are not copied whole): no per-row
+    copy, and the index arrays cover at most _GATHER_BLOCK bytes of text at a time (whole rows; a
+    longer row goes alone).  -> (body uint8, offsets uint64 [k n + 1])."""
+    k, n = len(cols), cols[0][1].size
+    lens = np.empty(k * n, np.int64)
+    for j, (_, _, ln) in enumerate(cols):
+        lens[j::k] = ln
+    offs = np.zeros(k * n + 1, np.int64)
+    np.cumsum(lens, out=offs[1:])
+    body = np.empty(int(offs[-1]), np.uint8)
+    for j, (values, st, ln) in enumerate(cols):
+        dst = offs[:-1][j::k]  # where the column's rows go
+        cum = np.zeros(n + 1, np.int64)
+        np.cumsum(ln, out=cum[1:])
+        r0 = 0
+        while r0 < n:
+            r1 = int(np.searchsorted(cum, cum[r0] + _GATHER_BLOCK, "right")) - 1
+            r1 = min(max(r1, r0 + 1), n)
+            tot = int(cum[r1] - cum[r0])
+            if tot:
+                l = ln[r0:r1]
+                within = np.arange(tot, dtype=np.int64) - np.repeat(cum[r0:r1] - cum[r0], l)
+                body[np.repeat(dst[r0:r1], l) + within] = values[np.repeat(st[r0:r1], l) + within]
+            r0 = r1
+    return body, offs.astype(np.uint64)
+
+
+def arena_from_batch(batch, text_col="sentence", label_col="labels", alt_column=None) -> ArrowArena:
+    """One record batch -> text arena + offsets + label arrays, read straight
+    from the Arrow buffers (nulls are taken as empty text / no labels).
+    alt_column: a second utf8 column -- the arena holds the rows of both interleaved (text range
+    2r is text_col's row r, range 2r + 1 alt_column's: what the pair calls take), 2n + 1 offsets,
+    and the labels stay one set per row."""
+    pa = _pa()
+    values, starts, lens = _utf8_column(batch, text_col)
+    n = lens.size
+    if alt_column is not None:
+        body, offs = _interleave([(values, starts, lens), _utf8_column(batch, alt_column)])
+    elif n and (starts[1:] != starts[:-1] + lens[:-1]).any():  # null rows over non-empty slots
+        body, offs = _interleave([(values, starts, lens)])
+    else:
+        base = int(starts[0]) if n else 0
+        end = base + int(lens.sum())
+        body = values[base:end]
         offs = np.zeros(n + 1, np.uint64)
         np.cumsum(lens, out=offs[1:])
-    else:
-        base, end = int(o[0]), int(o[-1])
-        body = np.frombuffer(vbuf, np.uint8, count=end - base, offset=base) if end > base else np.zeros(0, np.uint8)
-        offs = (o - base).astype(np.uint64)
     arena = np.concatenate([body, np.zeros(16, np.uint8)])
 
     lc = batch.column(batch.schema.get_field_index(label_col))

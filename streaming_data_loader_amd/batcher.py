@@ -61,11 +61,15 @@ class Span:
 @dataclass
 class MultiLabel:
     number_labels: int = 9
+    # sdl_config.pair (DESIGN.md §3 "Sentence pairs"): two texts per example (SimpleData.text and
+    # .alt_text) in one [CLS] A [SEP] B [SEP] row with token types; off = the reference's rows
+    pair: bool = False
 
 
 @dataclass
 class SingleClass:
     """DataSetConfig::SingleClass (dataset_config.rs; single_cases.rs: Imdb)."""
+    pair: bool = False  # as MultiLabel.pair
 
 
 DataSetConfig = Union[Mask, Gpt, Span, MultiLabel, SingleClass]
@@ -205,6 +209,8 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
         c.span_policy, c.span_noise_per_mille = dataset_config.policy, dataset_config.noise_per_mille
     if isinstance(dataset_config, MultiLabel):
         c.number_labels = dataset_config.number_labels
+    if isinstance(dataset_config, (MultiLabel, SingleClass)):
+        c.pair = 1 if dataset_config.pair else 0
     c.seed, c.device, c.first_record, c.rng_mode = seed, device, first_record, rng_mode
     if mask_policy is not None:
         c.mask_policy = mask_policy
@@ -336,17 +342,29 @@ class _NativeBatcher(Batcher):
                                                           0 if lab is None else lab.size, ctypes.byref(b)))
         return _dataset_from(b, self.kind) if got else None
 
-    def push_arena(self, arena, offsets, labels=None, label_offsets=None):
+    def _push_pair(self, a: bytes, b: bytes, labels) -> Optional[DataSet]:
+        out = native.Batch()
+        lab = np.ascontiguousarray(labels, np.uint32)
+        got = native.check(native.load().sdl_batcher_push_pair(self._h, a, len(a), b, len(b), lab.ctypes.data,
+                                                               lab.size, ctypes.byref(out)))
+        return _dataset_from(out, self.kind) if got else None
+
+    def push_arena(self, arena, offsets, labels=None, label_offsets=None, pairs=False):
         """sdl_batcher_push_many over a host arena (uint8) + uint64 offsets
         (+ uint32 label values / uint64 label offsets); returns the batches
-        the same sequence of create_sync_batch calls would have emitted."""
+        the same sequence of create_sync_batch calls would have emitted.
+        pairs: sdl_batcher_push_many_pairs -- text range 2r is A_r and 2r + 1 is B_r of example r
+        (2n + 1 offsets, n + 1 label offsets)."""
         arena = np.ascontiguousarray(arena, np.uint8)
         offsets = np.ascontiguousarray(offsets, np.uint64)
         n = ctypes.c_size_t()
         lv = None if labels is None else np.ascontiguousarray(labels, np.uint32)
         lo = None if label_offsets is None else np.ascontiguousarray(label_offsets, np.uint64)
-        native.check(native.load().sdl_batcher_push_many(
-            self._h, arena.ctypes.data, offsets.ctypes.data, offsets.size - 1,
+        if pairs and (offsets.size - 1) % 2:
+            raise ValueError("pairs need an even number of text ranges")
+        fn = native.load().sdl_batcher_push_many_pairs if pairs else native.load().sdl_batcher_push_many
+        native.check(fn(
+            self._h, arena.ctypes.data, offsets.ctypes.data, (offsets.size - 1) // 2 if pairs else offsets.size - 1,
             None if lv is None or lv.size == 0 else lv.ctypes.data, None if lo is None else lo.ctypes.data,
             ctypes.byref(n)))
         out = []
@@ -399,39 +417,59 @@ class SimpleBatcher(_NativeBatcher):
         return cls(cfg.model_config, cfg.dataset_config, cfg.batch, cfg.tokenizer, cfg.seed, cfg.device,
                    rng_mode=cfg.rng_mode)
 
-    def create_sync_batch(self, data: SimpleTransport) -> Optional[DataSet]:
-        text = data.data.text
-        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    @property
+    def pair(self):
+        return bool(self.dataset_config.pair)
+
+    def _texts(self, data: SimpleData):
+        """The record's text ranges as bytes: [text], or [text, alt_text] on a pair batcher (the
+        reference tokenizes alt_text and drops it, dataset.rs:47)."""
+        def raw(t):
+            return t.encode("utf-8") if isinstance(t, str) else bytes(t)
+        if not self.pair:
+            return [raw(data.text)]
+        if data.alt_text is None:
+            raise ValueError("a pair batcher needs SimpleData.alt_text (it may be empty, not None)")
+        return [raw(data.text), raw(data.alt_text)]
+
+    def _labels(self, label):
         if isinstance(self.dataset_config, SingleClass):
-            if data.label is None or data.label.single is None:
+            if label is None or label.single is None:
                 # the reference's label.map(push) would skip the label and misalign the
                 # label list; SingleClassArrowGenerator always yields Some(Label::Single)
                 raise ValueError("single-class records carry exactly one Label::Single")
-            return self._push(raw, [data.label.single])
-        if data.label is None or data.label.multi is None:
+            return [label.single]
+        if label is None or label.multi is None:
             raise ValueError("Label Type Not Supported")  # bert_data.rs:75 panics
-        return self._push(raw, data.label.multi)
+        return label.multi
+
+    def create_sync_batch(self, data: SimpleTransport) -> Optional[DataSet]:
+        texts, labels = self._texts(data.data), self._labels(data.label)
+        if self.pair:
+            return self._push_pair(texts[0], texts[1], labels)
+        return self._push(texts[0], labels)
 
     def create_sync_batches(self, items):
         """create_sync_batch over many SimpleTransport records in one device pass."""
-        blobs = [t.data.text.encode("utf-8") if isinstance(t.data.text, str) else bytes(t.data.text) for t in items]
+        blobs = [b for t in items for b in self._texts(t.data)]
         offs = np.zeros(len(blobs) + 1, np.uint64)
         np.cumsum([len(x) for x in blobs], out=offs[1:])
         arena = np.frombuffer(b"".join(blobs) + b"\0" * 16, np.uint8)
-        single = isinstance(self.dataset_config, SingleClass)
-        vals, loffs = _pack_labels([[t.label.single] if single else t.label.multi for t in items])
-        return self.push_arena(arena, offs, vals, loffs)
+        vals, loffs = _pack_labels([self._labels(t.label) for t in items])
+        return self.push_arena(arena, offs, vals, loffs, pairs=self.pair)
 
-    def push_arrow(self, record_batch, text_col=None, label_col=None):
+    def push_arrow(self, record_batch, text_col=None, label_col=None, alt_col=None):
         """create_sync_batch for every row of an Arrow record batch with the
         MultiArrowGenerator schema (sentence, labels: list<int64>) or the
         SingleClassArrowGenerator one (text, label: int64), fed from the column
-        buffers directly."""
+        buffers directly.  A pair batcher names its second utf8 column in alt_col."""
         from .arrow_io import arena_from_batch
         single = isinstance(self.dataset_config, SingleClass)
+        if self.pair != (alt_col is not None):
+            raise ValueError("alt_col goes with a pair batcher, and a pair batcher needs it")
         a = arena_from_batch(record_batch, text_col or ("text" if single else "sentence"),
-                             label_col or ("label" if single else "labels"))
-        return self.push_arena(a.arena, a.offsets, a.labels, a.label_offsets)
+                             label_col or ("label" if single else "labels"), alt_column=alt_col)
+        return self.push_arena(a.arena, a.offsets, a.labels, a.label_offsets, pairs=self.pair)
 
 
 def create_batch(rx, tx, batcher: Batcher):

@@ -463,6 +463,8 @@ struct sdl_batcher {
     // HostBatch.tt); the public token_type_ids stays NULL
     bool pack() const { return cfg.pack == 1; }
     bool plane4() const { return with_tt() || pack(); }
+    // sdl_config.pair = 1: a call's 2 n text ranges are n examples of two texts, one row each (pair.hip)
+    bool pair() const { return cfg.pair == 1; }
 
     std::shared_ptr<BatchPool> pool;
     HostBatch *new_batch() {
@@ -485,6 +487,9 @@ struct sdl_batcher {
     PackParams pack_params(int64_t R, int64_t rows_cap);
     void run_pack(int64_t R, int64_t rows_cap, hipStream_t st);
     void run_pack_flush(hipStream_t st);
+    DevBuf<uint32_t> pair_rb;  // pair = 1: the label kernels' record bounds {0, n_pairs}
+    void run_pair(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st,
+                  const uint32_t *d_labels, const uint64_t *d_label_off);
     int64_t rows_capacity(int64_t N, int64_t R) const;
     void run_device(const uint8_t *d_text, int64_t N, const uint64_t *d_off, int64_t R, uint64_t first_record,
                     hipStream_t st, const uint32_t *d_labels = nullptr, const uint64_t *d_label_off = nullptr);

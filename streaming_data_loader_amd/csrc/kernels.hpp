@@ -410,6 +410,24 @@ hipError_t launch_pack_rows(const PackParams &q, hipStream_t st);
 // the carry as one last row (0 rows when it is empty), rows < B of the planes; the new carry is empty
 hipError_t launch_pack_flush(const PackParams &q, hipStream_t st);
 
+// pair.hip: one [CLS] A [SEP] B [SEP] row per example of two texts (sdl_config.pair = 1, DESIGN.md §3
+// "Sentence pairs"), after launch_records over the 2 * n_pairs text ranges.  A struct of its own, not
+// fields of RowParams (see MaskPolicy): the unpaired kernels compile to what they were.
+struct PairParams {
+    const uint16_t *lists;                    // the WordPiece chunk lists as the tokenizer wrote them (TokSrc.lists):
+    const uint32_t *chunk_off;                //   no dense copy of the ids -- a row keeps at most S - 3 of its pair's
+    const uint64_t *off;                      //   [2 n_pairs + 1] text ranges: the chunks a side's ids lie in
+    int64_t n_lists;                          //   chunks of the call
+    const uint32_t *rec_tok, *rec_cnt;        // text range q's first id / id count (A_r: 2r, B_r: 2r + 1)
+    int64_t n_pairs;                          // rows the call fills
+    int64_t rows_end;                         // min(n_pairs rounded up to B, the planes' rows): rows_end * S < 2^32
+    int32_t S, cls, sep, pad;                 // the tokenizer's own [CLS] / [SEP] ids, not RowParams.pre / post
+    int32_t *ids, *am, *tt;                   // planes [rows_end .., S]: every column of every row < rows_end is written
+    uint32_t *row_off, *row_rec, *rb;         // out: row_off[r] = r (r <= n_pairs), row_rec[g] = g, rb = {0, n_pairs} --
+                                              // what k_single_labels / k_multi_labels read, a row per pair
+};
+hipError_t launch_rows_pair(const PairParams &q, hipStream_t st);
+
 // rng_mode 1 masks (pipeline.hip): the rows rand_pre_slot names (chunk 0 of every record, chunk 1
 // of long ones) from (seed, first_record + r, chunk) alone -- launched beside the tokenizer: swap
 // indices (lane per row) into jbuf [2 R, S], then the mask bits into P.mask_bits0 slots

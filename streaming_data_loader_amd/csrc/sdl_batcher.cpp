@@ -98,6 +98,40 @@ void sdl_batcher::run_pack_flush(hipStream_t st) {
     last_R = 0;
 }
 
+// pair = 1: the call's rows from rec_tok / rec_cnt of its 2 n text ranges (after launch_records), one
+// launch for the three planes, then the task's label kernel over n rows -- no host synchronisation
+void sdl_batcher::run_pair(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st,
+                           const uint32_t *d_labels, const uint64_t *d_label_off) {
+    const int64_t n = R / 2;
+    pair_rb.ensure(2);
+    PairParams q{};
+    q.lists = reinterpret_cast<const uint16_t *>(tokc.p);
+    q.chunk_off = chunk_off.p;
+    q.off = d_off;
+    q.n_lists = n_chunks;
+    q.rec_tok = rec_tok.p;
+    q.rec_cnt = rec_cnt.p;
+    q.n_pairs = n;
+    q.rows_end = std::min<int64_t>((n + P.B - 1) / P.B * P.B, rows_cap);
+    q.S = P.S;
+    q.cls = tok.tpl_cls;  // (the loaded BertProcessing's own ids: P.pre / P.post hold the reference's doubled framing)
+    q.sep = tok.tpl_sep;
+    q.ids = o_ids.p;
+    q.am = o_am.p;
+    q.tt = o_tt.p;
+    q.row_off = row_off.p;
+    q.row_rec = row_rec.p;
+    q.rb = pair_rb.p;
+    HIP_TRY(launch_rows_pair(q, st));
+    const SegSel sel{pair_rb.p, 0, 1};
+    if (multi())
+        HIP_TRY(launch_multi_labels(d_labels, d_label_off, row_rec.p, row_off.p, sel, rows_cap, P.B, P.label_width,
+                                    o_f32.p, lab_err.p, st));
+    else
+        HIP_TRY(launch_single_labels(d_labels, d_label_off, row_rec.p, row_off.p, sel, rows_cap, P.B, o_lab.p,
+                                     lab_err.p, st));
+}
+
 int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     // rows <= sum_r ceil((ids_r + frame) / S) with ids_r <= bytes_r
     const int64_t F = P.n_pre + P.n_post;
@@ -105,6 +139,7 @@ int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     const int64_t ids = dt.kind == TOK_UNIGRAM ? 2 * N + 1024 * 1024 : N;
     int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
     if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
+    if (pair()) cap = R / 2;                          // a row per pair of text ranges
     return (cap + P.B - 1) / P.B * P.B;
 }
 
@@ -115,6 +150,8 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
     // (pack.hip indexes the planes and the stream with 32 bits)
     if (pack() && rows_cap * P.S > ((int64_t)1 << 32) - 4096)
         throw CapacityError("pack: the call's rows exceed 2^32 positions");
+    if (pair() && rows_cap * P.S > ((int64_t)1 << 32) - 4096)  // (pair.hip: a flat 32-bit work index)
+        throw CapacityError("pair: the call's rows exceed 2^32 positions");
     ranges.ensure((size_t)std::max<int64_t>(n_chunks, 1) * 3);
     // a chunk's list: STAGE u16 (WordPiece), STAGE / UNI_STAGE u32 entries (BPE / Unigram)
     const bool wp = dt.kind != TOK_BYTE_BPE && dt.kind != TOK_UNIGRAM;
@@ -166,7 +203,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
     // whole call, so they run as one segment.
     SegChunks sc{};
     sc.K = 1;
-    if (!bpe && !uni && seg_target > 1 && n_chunks >= 2 * seg_min_chunks) {
+    if (!bpe && !uni && !pair() && seg_target > 1 && n_chunks >= 2 * seg_min_chunks) {
         sc.K = (int)std::min<int64_t>(seg_target, n_chunks / seg_min_chunks);
         sc.K = std::min(sc.K, MAX_SEGMENTS);
     }
@@ -178,13 +215,14 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
     auto mark = [&](int i) {
         if (profiling) HIP_TRY(hipEventRecord(ev[i], st));
     };
-    // (pack = 1 takes the plain one-segment sequence up to launch_records, then pack.hip)
-    const bool small = !piped && !profiling && !pack() && n_chunks <= SMALL_CHUNKS && R <= 8192;
+    // (pack = 1 takes the plain one-segment sequence up to launch_records, then pack.hip; pair = 1
+    // the same without the dense copy of the ids, then pair.hip)
+    const bool small = !piped && !profiling && !pack() && !pair() && n_chunks <= SMALL_CHUNKS && R <= 8192;
     // WordPiece, large calls: k_rows reads the chunk lists themselves -- no dense copy of the
     // ids (span's rows kernels and the small-call kernels read the dense array)
-    const bool from_lists = wp && !small && !span();
+    const bool from_lists = wp && !small && !span();  // (pair = 1 too: k_rows_pair reads the lists)
     if (!from_lists) tok_ids.ensure(tok_ids_n);
-    else row_chunk.ensure((size_t)std::max<int64_t>(rows_cap, 1));
+    else if (!pair()) row_chunk.ensure((size_t)std::max<int64_t>(rows_cap, 1));  // (k_rows_pair searches the chunks itself)
     uint16_t *const lists = reinterpret_cast<uint16_t *>(tokc.p);
     mark(0);
     // (one segment: k_chunk_ranges also writes its record bounds and zeroes the label error word)
@@ -268,13 +306,18 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
         // one segment past the one-workgroup scan: k_records leaves the row scan's tile sums
         // (scan_tmp: the chunk scan before it on the stream is done with them) and one launch
         // scans the rows and maps them, in place of reduce, sums, apply and k_row_map
-        const bool scan_map = !piped && !pack() && R > scan_small_max();
+        const bool scan_map = !piped && !pack() && !pair() && R > scan_small_max();
         HIP_TRY(launch_records(p, d_off, R, N, chunk_off.p, n_chunks, rec_local.p, rec_tok.p, rec_cnt.p, rec_rows.p,
                                sel, s, scan_map ? scan_tmp.p : nullptr));
         if (!piped) mark(5);
         if (pack()) {  // rec_tok / rec_cnt exist: the stream's rows instead of row scan, row map and k_rows
             mark(6);
             run_pack(R, rows_cap, s);
+            return;
+        }
+        if (pair()) {  // a row per pair of text ranges instead of row scan, row map and k_rows
+            mark(6);
+            run_pair(R, rows_cap, n_chunks, d_off, s, d_labels, d_label_off);
             return;
         }
         // (segment k's rows read lists and offsets of chunks < cz only: all written by now)
@@ -455,12 +498,14 @@ void sdl_batcher::queue_packed_rows() {
 void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, int64_t R, const uint32_t *labels,
                                const uint64_t *label_off) {
     const int64_t N = (int64_t)offsets[R];
+    // pair = 1: R text ranges are E = R / 2 examples -- one label set, one row, one cadence step each
+    const int64_t E = pair() ? R / 2 : R;
     // one pinned staging blob, one H2D: text | offsets | labels | label offsets
     const bool with_labels = simple() && labels && label_off;  // validated by the caller
-    const uint64_t L = with_labels ? label_off[R] - label_off[0] : 0;
+    const uint64_t L = with_labels ? label_off[E] - label_off[0] : 0;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t x_off = up((size_t)N + 16), x_lab = up(x_off + 8 * (size_t)(R + 1)),
-                 x_loff = up(x_lab + 4 * (size_t)L + 4), blob = x_loff + 8 * (size_t)(R + 1);
+                 x_loff = up(x_lab + 4 * (size_t)L + 4), blob = x_loff + 8 * (size_t)(E + 1);
     pin_blob.ensure(blob + 16);  // (+16: k_chunk_ranges copies whole 16-B units)
     h2d_blob.ensure(blob + 16);
     HostClock hc;
@@ -473,7 +518,7 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
     if (with_labels) {  // Label::Multi indices / Label::Single
         std::memcpy(pin_blob.p + x_lab, labels, sizeof(uint32_t) * (size_t)L);
         uint64_t *lo = reinterpret_cast<uint64_t *>(pin_blob.p + x_loff);
-        for (int64_t r = 0; r <= R; ++r) lo[r] = label_off[r] - label_off[0];
+        for (int64_t r = 0; r <= E; ++r) lo[r] = label_off[r] - label_off[0];
         d_labels = reinterpret_cast<const uint32_t *>(h2d_blob.p + x_lab);
         d_label_off = reinterpret_cast<const uint64_t *>(h2d_blob.p + x_loff);
         h2d_bytes = blob;
@@ -499,7 +544,7 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
     // Small calls (a per-record push): the rows go straight to the back batch
     // and a pre-allocated next one in the same pass, and the row offsets and
     // error words come back through mapped memory -- one synchronisation.
-    const bool direct = R <= 4096 && N <= ((int64_t)1 << 20) && !store.empty() && !profiling && !pack();
+    const bool direct = R <= 4096 && N <= ((int64_t)1 << 20) && !store.empty() && !profiling && !pack() && !pair();
     uint32_t cap = 0;
     const uint32_t *stat;
     DirectDst dd{};
@@ -555,24 +600,24 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
         stat = pin_stat.p;
     } else {
         hc.lap("enqueue");
-        pin_u32.ensure((size_t)R + 3);
-        HIP_TRY(hipMemcpyAsync(pin_u32.p, row_off.p, sizeof(uint32_t) * (size_t)(R + 1), hipMemcpyDeviceToHost,
+        pin_u32.ensure((size_t)E + 3);
+        HIP_TRY(hipMemcpyAsync(pin_u32.p, row_off.p, sizeof(uint32_t) * (size_t)(E + 1), hipMemcpyDeviceToHost,
                                stream));
-        pin_u32.p[R + 1] = pin_u32.p[R + 2] = 0;
-        if (span()) HIP_TRY(hipMemcpyAsync(pin_u32.p + R + 1, span_err.p, 4, hipMemcpyDeviceToHost, stream));
+        pin_u32.p[E + 1] = pin_u32.p[E + 2] = 0;
+        if (span()) HIP_TRY(hipMemcpyAsync(pin_u32.p + E + 1, span_err.p, 4, hipMemcpyDeviceToHost, stream));
         if (dt.kind == TOK_UNIGRAM)
-            HIP_TRY(hipMemcpyAsync(pin_u32.p + R + 2, uni_err.p, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(pin_u32.p + E + 2, uni_err.p, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         hc.lap("h2d+kernels");
         stat = pin_u32.p;
     }
     // where the reference panics (t5_data.rs:205-216: a label past S/4 or a
     // 101st sentinel) the host path fails the call before any batch is queued
-    if (stat[R + 1])
-        throw ArgError("span: " + std::to_string(stat[R + 1]) +
+    if (stat[E + 1])
+        throw ArgError("span: " + std::to_string(stat[E + 1]) +
                        " label/sentinel writes out of range (the reference panics)");
-    if (stat[R + 2])
-        throw CapacityError("t5 tokenizer capacity exceeded (flags " + std::to_string(stat[R + 2]) + ")");
+    if (stat[E + 2])
+        throw CapacityError("t5 tokenizer capacity exceeded (flags " + std::to_string(stat[E + 2]) + ")");
     // GenTokenizer::create_sync_batch per record (gen_batcher.rs:69-94):
     // rows fill the back batch (handle_internal_batch per chunk), at most
     // one finished batch is emitted per record.  Each run of rows landing
@@ -583,7 +628,7 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
         uint32_t dst, g0, n;
     };
     std::vector<Seg> segs;
-    for (int64_t r = 0; r < R; ++r) {
+    for (int64_t r = 0; r < E; ++r) {
         const uint32_t g0 = stat[r], g1 = stat[r + 1];
         if (g1 > g0 && store.empty())  // store.back_mut().unwrap() (gen_batcher.rs:45) panics
             throw ArgError("a record after get_working_batch emptied the batch store (the reference panics)");
@@ -626,7 +671,7 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
     if (!segs.empty()) HIP_TRY(hipStreamSynchronize(stream));
     hc.lap("d2h");
     hc.report(N, segs.size(), pool ? pool->fresh : 0);
-    n_records += (uint64_t)R;
+    n_records += (uint64_t)E;
 }
 
 namespace {
@@ -705,6 +750,17 @@ int check_config(const sdl_config *cfg) {
     if (cfg->task != SDL_TASK_MLM && cfg->task != SDL_TASK_CLM && cfg->task != SDL_TASK_MULTI_LABEL &&
         cfg->task != SDL_TASK_SPAN && cfg->task != SDL_TASK_SINGLE_CLASS)
         return fail(SDL_ERR_UNSUPPORTED, "unknown task");
+    // (sentence pairs first: a task or tokenizer they are not built for is named as that)
+    if (cfg->pair != 0 && cfg->pair != 1)
+        return fail(SDL_ERR_ARG, "pair must be 0 (one text per record) or 1 (sentence pairs); other values are reserved");
+    if (cfg->pair == 1) {
+        if (cfg->task != SDL_TASK_SINGLE_CLASS && cfg->task != SDL_TASK_MULTI_LABEL)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pair = 1 with task mlm, clm or span: sentence pairs are built for the single-class and "
+                        "multi-label tasks only");
+        if (cfg->sequence_length < 3)
+            return fail(SDL_ERR_ARG, "pair = 1 needs sequence_length >= 3: [CLS] A [SEP] B [SEP]");
+    }
     if (cfg->task == SDL_TASK_SPAN && (cfg->sequence_length < 4 || !(cfg->avg_span_gap == cfg->avg_span_gap) ||
                                        !(cfg->avg_span_size == cfg->avg_span_size)))
         return fail(SDL_ERR_ARG, "span needs sequence_length >= 4 and finite avg_span_gap / avg_span_size");
@@ -948,6 +1004,70 @@ int check_labels(const sdl_batcher *h, const uint32_t *labels, size_t n) {
     return SDL_OK;
 }
 
+// sdl_batcher_push_many / _push_many_pairs behind their handle checks: n_records text ranges are
+// n_examples examples (the same, or half as many), each with one set of labels
+int push_many_checked(sdl_batcher *h, const uint8_t *arena, const uint64_t *offsets, size_t n_records,
+                             size_t n_examples, const uint32_t *labels, const uint64_t *label_offsets,
+                             size_t *n_emitted) {
+    if (h->multi() && label_offsets) {
+        if (!labels && label_offsets[n_examples] != label_offsets[0]) return fail(SDL_ERR_ARG, "null labels");
+        for (size_t r = 0; r < n_examples; ++r)
+            if (label_offsets[r + 1] < label_offsets[r]) return fail(SDL_ERR_ARG, "label_offsets must be non-decreasing");
+        if (int rc = check_labels(h, labels + label_offsets[0], label_offsets[n_examples] - label_offsets[0])) return rc;
+    }
+    if (h->single()) {
+        if (!label_offsets || !labels) return fail(SDL_ERR_ARG, "single-class records need their labels");
+        for (size_t r = 0; r < n_examples; ++r)
+            if (label_offsets[r + 1] != label_offsets[r] + 1)
+                return fail(SDL_ERR_ARG, "single-class records carry exactly one label");
+    }
+    if (offsets[0] != 0) return fail(SDL_ERR_ARG, "offsets[0] must be 0");
+    for (size_t r = 0; r < n_records; ++r)
+        if (offsets[r + 1] < offsets[r]) return fail(SDL_ERR_ARG, "offsets must be non-decreasing");
+    if (offsets[n_records] >= (1ull << 32)) return fail(SDL_ERR_CAPACITY, "arena must be < 4 GiB per call");
+    return guarded(SDL_ERR_CAPACITY, SDL_ERR_ARG, [&]() -> int {
+        const size_t before = h->outbox.size();
+        if (n_records)
+            h->process_host(arena, offsets, (int64_t)n_records, labels ? labels + (label_offsets ? label_offsets[0] : 0) : nullptr,
+                            label_offsets);
+        if (n_emitted) *n_emitted = h->outbox.size() - before;
+        return SDL_OK;
+    });
+}
+
+// sdl_process_device_labels / _pairs behind their handle checks: n_records text ranges give
+// n_examples examples (the same, or half as many); d_rows is row_off[n_examples]
+int process_device_checked(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len, const uint64_t *d_offsets,
+                                  uint64_t n_records, uint64_t n_examples, const uint32_t *d_labels,
+                                  const uint64_t *d_label_offsets, uint64_t first_record, void *stream,
+                                  sdl_device_rows *out) {
+    if ((d_labels == nullptr) != (d_label_offsets == nullptr)) return fail(SDL_ERR_ARG, "labels need label offsets");
+    if (text_len >= (1ull << 32)) return fail(SDL_ERR_CAPACITY, "arena must be < 4 GiB per call");
+    if (((uintptr_t)d_text & 15u) != 0) return fail(SDL_ERR_ARG, "d_text must be 16-byte aligned");
+    return guarded(SDL_ERR_ARG, SDL_ERR_ARG, [&]() -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+        h->run_device(d_text, (int64_t)text_len, d_offsets, (int64_t)n_records, first_record, st, d_labels,
+                      d_label_offsets);
+        std::memset(out, 0, sizeof(*out));
+        out->input_ids = h->o_ids.p;
+        out->attention_mask = h->o_am.p;
+        out->token_type_ids = h->with_tt() ? h->o_tt.p : nullptr;
+        out->labels = h->multi() ? nullptr : h->o_lab.p;
+        out->labels_f32 = h->multi() ? h->o_f32.p : nullptr;
+        out->d_label_errors = h->simple() ? h->lab_err.p : h->span() ? h->span_err.p : nullptr;
+        out->d_tokenize_errors = h->dt.kind == TOK_UNIGRAM    ? h->uni_err.p
+                                 : h->dt.kind == TOK_BYTE_BPE && h->long_count.p
+                                     ? h->long_count.p + BPE_LONG_ERR  // k_bpe_long's list overflow
+                                     : nullptr;
+        out->d_rows = h->pack() ? h->pk_meta.p : h->row_off.p + n_examples;
+        out->d_record_rows = h->rec_rows.p;
+        out->d_tokens = h->chunk_off.p + (text_len + CHUNK - 1) / CHUNK;
+        out->rows_capacity = (uint64_t)h->last_rows_cap;
+        out->label_width = h->P.label_width;
+        return SDL_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -997,6 +1117,10 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             return fail(SDL_ERR_UNSUPPORTED,
                         "pack = 1 needs a byte-level BPE tokenizer with an <|endoftext|> id: packed rows are "
                         "not built for WordPiece or Unigram tokenizers");
+        if (cfg->pair == 1 && (h->tok.kind != TOK_WORDPIECE || h->tok.cls_id < 0 || h->tok.sep_id < 0))
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pair = 1 with a byte-level BPE or Unigram tokenizer: sentence pairs need a WordPiece "
+                        "tokenizer with [CLS] and [SEP] ids");
         HIP_TRY(hipSetDevice(h->device));
         {  // the handle's stream at the highest priority (stream2's background work yields to it)
             int least = 0, greatest = 0;
@@ -1023,6 +1147,7 @@ void sdl_batcher_destroy(sdl_batcher *h) { delete h; }
 int sdl_batcher_push(sdl_batcher *h, const uint8_t *utf8, size_t len, const uint32_t *labels, size_t n_labels,
                      sdl_batch *out) {
     if (!h || (!utf8 && len) || (!labels && n_labels)) return fail(SDL_ERR_ARG, "null argument");
+    if (h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push on a handle created with pair = 1: use sdl_batcher_push_pair");
     if (h->multi()) {
         if (int rc = check_labels(h, labels, n_labels)) return rc;
     }
@@ -1055,29 +1180,45 @@ int sdl_batcher_push(sdl_batcher *h, const uint8_t *utf8, size_t len, const uint
 int sdl_batcher_push_many(sdl_batcher *h, const uint8_t *arena, const uint64_t *offsets, size_t n_records,
                           const uint32_t *labels, const uint64_t *label_offsets, size_t *n_emitted) {
     if (!h || !offsets || (!arena && n_records && offsets[n_records])) return fail(SDL_ERR_ARG, "null argument");
-    if (h->multi() && label_offsets) {
-        if (!labels && label_offsets[n_records] != label_offsets[0]) return fail(SDL_ERR_ARG, "null labels");
-        for (size_t r = 0; r < n_records; ++r)
-            if (label_offsets[r + 1] < label_offsets[r]) return fail(SDL_ERR_ARG, "label_offsets must be non-decreasing");
-        if (int rc = check_labels(h, labels + label_offsets[0], label_offsets[n_records] - label_offsets[0])) return rc;
+    if (h->pair())
+        return fail(SDL_ERR_STATE, "sdl_batcher_push_many on a handle created with pair = 1: use sdl_batcher_push_many_pairs");
+    return push_many_checked(h, arena, offsets, n_records, n_records, labels, label_offsets, n_emitted);
+}
+
+int sdl_batcher_push_many_pairs(sdl_batcher *h, const uint8_t *arena, const uint64_t *offsets, size_t n_pairs,
+                                const uint32_t *labels, const uint64_t *label_offsets, size_t *n_emitted) {
+    if (!h || !offsets || (!arena && n_pairs && offsets[2 * n_pairs])) return fail(SDL_ERR_ARG, "null argument");
+    if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push_many_pairs needs a handle created with pair = 1");
+    return push_many_checked(h, arena, offsets, 2 * n_pairs, n_pairs, labels, label_offsets, n_emitted);
+}
+
+// One example of two texts: push_many_pairs of one pair, staged back to back (the bulk path's
+// launches and two synchronisations a call; a tuned one-pair push is not built).
+int sdl_batcher_push_pair(sdl_batcher *h, const uint8_t *a, size_t len_a, const uint8_t *b, size_t len_b,
+                          const uint32_t *labels, size_t n_labels, sdl_batch *out) {
+    if (!h || (!a && len_a) || (!b && len_b) || (!labels && n_labels)) return fail(SDL_ERR_ARG, "null argument");
+    if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push_pair needs a handle created with pair = 1");
+    if (h->multi()) {
+        if (int rc = check_labels(h, labels, n_labels)) return rc;
     }
-    if (h->single()) {
-        if (!label_offsets || !labels) return fail(SDL_ERR_ARG, "single-class records need their labels");
-        for (size_t r = 0; r < n_records; ++r)
-            if (label_offsets[r + 1] != label_offsets[r] + 1)
-                return fail(SDL_ERR_ARG, "single-class records carry exactly one label");
-    }
-    if (offsets[0] != 0) return fail(SDL_ERR_ARG, "offsets[0] must be 0");
-    for (size_t r = 0; r < n_records; ++r)
-        if (offsets[r + 1] < offsets[r]) return fail(SDL_ERR_ARG, "offsets must be non-decreasing");
-    if (offsets[n_records] >= (1ull << 32)) return fail(SDL_ERR_CAPACITY, "arena must be < 4 GiB per call");
+    if (h->single() && n_labels != 1) return fail(SDL_ERR_ARG, "single-class records carry exactly one label");
+    if ((uint64_t)len_a + (uint64_t)len_b >= (1ull << 32)) return fail(SDL_ERR_CAPACITY, "record too large");
     return guarded(SDL_ERR_CAPACITY, SDL_ERR_ARG, [&]() -> int {
+        std::vector<uint8_t> both(len_a + len_b);
+        if (len_a) std::memcpy(both.data(), a, len_a);
+        if (len_b) std::memcpy(both.data() + len_a, b, len_b);
+        uint64_t offs[3] = {0, (uint64_t)len_a, (uint64_t)(len_a + len_b)};
+        uint64_t loffs[2] = {0, (uint64_t)n_labels};
         const size_t before = h->outbox.size();
-        if (n_records)
-            h->process_host(arena, offsets, (int64_t)n_records, labels ? labels + (label_offsets ? label_offsets[0] : 0) : nullptr,
-                            label_offsets);
-        if (n_emitted) *n_emitted = h->outbox.size() - before;
-        return SDL_OK;
+        h->process_host(both.empty() ? (const uint8_t *)"" : both.data(), offs, 2, labels, loffs);
+        if (h->outbox.size() > before) {
+            HostBatch *bt = h->outbox.back();
+            h->outbox.pop_back();
+            if (out) fill_batch(h, bt, out);
+            else delete bt;
+            return 1;
+        }
+        return 0;
     });
 }
 
@@ -1144,31 +1285,20 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
                               uint64_t n_records, const uint32_t *d_labels, const uint64_t *d_label_offsets,
                               uint64_t first_record, void *stream, sdl_device_rows *out) {
     if (!h || !out || !d_offsets || (!d_text && text_len)) return fail(SDL_ERR_ARG, "null argument");
-    if ((d_labels == nullptr) != (d_label_offsets == nullptr)) return fail(SDL_ERR_ARG, "labels need label offsets");
-    if (text_len >= (1ull << 32)) return fail(SDL_ERR_CAPACITY, "arena must be < 4 GiB per call");
-    if (((uintptr_t)d_text & 15u) != 0) return fail(SDL_ERR_ARG, "d_text must be 16-byte aligned");
-    return guarded(SDL_ERR_ARG, SDL_ERR_ARG, [&]() -> int {
-        hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-        h->run_device(d_text, (int64_t)text_len, d_offsets, (int64_t)n_records, first_record, st, d_labels,
-                      d_label_offsets);
-        std::memset(out, 0, sizeof(*out));
-        out->input_ids = h->o_ids.p;
-        out->attention_mask = h->o_am.p;
-        out->token_type_ids = h->with_tt() ? h->o_tt.p : nullptr;
-        out->labels = h->multi() ? nullptr : h->o_lab.p;
-        out->labels_f32 = h->multi() ? h->o_f32.p : nullptr;
-        out->d_label_errors = h->simple() ? h->lab_err.p : h->span() ? h->span_err.p : nullptr;
-        out->d_tokenize_errors = h->dt.kind == TOK_UNIGRAM    ? h->uni_err.p
-                                 : h->dt.kind == TOK_BYTE_BPE && h->long_count.p
-                                     ? h->long_count.p + BPE_LONG_ERR  // k_bpe_long's list overflow
-                                     : nullptr;
-        out->d_rows = h->pack() ? h->pk_meta.p : h->row_off.p + n_records;
-        out->d_record_rows = h->rec_rows.p;
-        out->d_tokens = h->chunk_off.p + (text_len + CHUNK - 1) / CHUNK;
-        out->rows_capacity = (uint64_t)h->last_rows_cap;
-        out->label_width = h->P.label_width;
-        return SDL_OK;
-    });
+    if (h->pair())
+        return fail(SDL_ERR_STATE, "sdl_process_device[_labels] on a handle created with pair = 1: use sdl_process_device_pairs");
+    return process_device_checked(h, d_text, text_len, d_offsets, n_records, n_records, d_labels, d_label_offsets,
+                                  first_record, stream, out);
+}
+
+int sdl_process_device_pairs(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len, const uint64_t *d_offsets,
+                             uint64_t n_pairs, const uint32_t *d_labels, const uint64_t *d_label_offsets,
+                             uint64_t first_record, void *stream, sdl_device_rows *out) {
+    if (!h || !out || !d_offsets || (!d_text && text_len)) return fail(SDL_ERR_ARG, "null argument");
+    if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_process_device_pairs needs a handle created with pair = 1");
+    if (n_pairs >= (1ull << 31)) return fail(SDL_ERR_CAPACITY, "too many pairs in one call");
+    return process_device_checked(h, d_text, text_len, d_offsets, 2 * n_pairs, n_pairs, d_labels, d_label_offsets,
+                                  first_record, stream, out);
 }
 
 int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out) {
@@ -1265,6 +1395,8 @@ struct sdl_multi {
 int sdl_multi_create(const sdl_config *cfg, const char *tokenizer_path, const char *data_dir, const int32_t *devices,
                      uint32_t n_devices, sdl_multi **out) {
     if (!cfg || !devices || !out || n_devices == 0) return fail(SDL_ERR_ARG, "null argument or no devices");
+    if (cfg->pair == 1)
+        return fail(SDL_ERR_UNSUPPORTED, "sdl_multi_create with pair = 1: sentence pairs are not sharded over several handles");
     std::unique_ptr<sdl_multi> m(new sdl_multi());
     m->next_record = cfg->first_record;
     for (uint32_t k = 0; k < n_devices; ++k) {

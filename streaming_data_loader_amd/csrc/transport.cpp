@@ -131,6 +131,8 @@ int sdl_json_to_frames(sdl_batcher *h, const uint8_t *jsonl, uint64_t len, uint6
                        sdl_frame_sink sink, void *user, sdl_json_frames_stats *stats) {
     if (!h || (!jsonl && len)) return fail(SDL_ERR_ARG, "null argument");
     const int task = h->cfg.task;
+    if (h->pair())
+        return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: pair = 1 is not supported (one text member a line)");
     if (task != SDL_TASK_MLM && task != SDL_TASK_CLM && task != SDL_TASK_SPAN)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: JSON lines carry text only (mlm, clm, span)");
     if (h->pack())

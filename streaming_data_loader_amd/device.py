@@ -154,7 +154,7 @@ class DeviceBatcher:
     def __init__(self, task=native.SDL_TASK_MLM, batch_size=256, sequence_length=512, mask_length=None,
                  mask_id=103, seed=0, device=0, tokenizer=native.BERT_PROXY_TOKENIZER, chunk=True, min_ids=None,
                  number_labels=9, avg_span_gap=16.0, avg_span_size=2.0, rng_mode=0, mask_policy=0,
-                 mask_per_mille=150, pack=0, span_policy=0, span_noise_per_mille=0):
+                 mask_per_mille=150, pack=0, span_policy=0, span_noise_per_mille=0, pair=False):
         L = native.load()
         c = native.default_config(task)
         c.batch_size, c.sequence_length = batch_size, sequence_length
@@ -164,6 +164,7 @@ class DeviceBatcher:
         c.rng_mode = rng_mode
         c.mask_policy, c.mask_per_mille = mask_policy, mask_per_mille
         c.pack = int(pack)
+        c.pair = int(pair)  # single-class / multi-label: sentence pairs (process_pairs)
         c.span_policy, c.span_noise_per_mille = span_policy, span_noise_per_mille
         c.avg_span_gap, c.avg_span_size = avg_span_gap, avg_span_size
         if min_ids is not None:
@@ -218,6 +219,19 @@ class DeviceBatcher:
             ctypes.c_void_p(labels_ptr or None), ctypes.c_void_p(label_offsets_ptr or None), first_record,
             ctypes.c_void_p(stream or None), ctypes.byref(out)))
         return DeviceResult(self._h, out, n_records, self.cfg.sequence_length, self.cfg.batch_size, self.cfg.device,
+                            stream)
+
+    def process_pairs(self, text_ptr, text_len, offsets_ptr, n_pairs, labels_ptr=0, label_offsets_ptr=0,
+                      first_record=0, stream=0):
+        """Sentence pairs (pair=True; sdl_process_device_pairs): A_r is text range 2r and B_r range
+        2r + 1 of the device arena (2 n_pairs + 1 offsets, arena_from_pairs); labels per pair
+        (n_pairs + 1 label offsets).  One [CLS] A [SEP] B [SEP] row per pair."""
+        out = native.DeviceRows()
+        native.check(native.load().sdl_process_device_pairs(
+            self._h, ctypes.c_void_p(text_ptr), text_len, ctypes.c_void_p(offsets_ptr), n_pairs,
+            ctypes.c_void_p(labels_ptr or None), ctypes.c_void_p(label_offsets_ptr or None), first_record,
+            ctypes.c_void_p(stream or None), ctypes.byref(out)))
+        return DeviceResult(self._h, out, n_pairs, self.cfg.sequence_length, self.cfg.batch_size, self.cfg.device,
                             stream)
 
     def json_text(self, jsonl_ptr, jsonl_len, stream=0):
@@ -310,3 +324,9 @@ def arena_from_texts(texts):
         np.cumsum([len(x) for x in blobs], out=offs[1:])
     arena = np.frombuffer(b"".join(blobs), np.uint8) if blobs else np.zeros(0, np.uint8)
     return arena, offs
+
+
+def arena_from_pairs(pairs):
+    """Host arena + uint64 offsets (2n + 1) for a list of (A, B) str/bytes pairs, interleaved as
+    the pair calls take them: text range 2r is A_r, range 2r + 1 is B_r."""
+    return arena_from_texts([t for p in pairs for t in p])

@@ -27,6 +27,7 @@ SDL_SPAN_REFERENCE, SDL_SPAN_T5 = 0, 1
 EXPORTS = [
     "sdl_config_default", "sdl_batcher_create", "sdl_batcher_destroy", "sdl_batcher_push",
     "sdl_batcher_push_many", "sdl_batcher_next", "sdl_batcher_flush", "sdl_batch_release",
+    "sdl_batcher_push_pair", "sdl_batcher_push_many_pairs", "sdl_process_device_pairs",
     "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids",
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
@@ -45,7 +46,9 @@ class SDLError(RuntimeError):
 class _PackWord(ctypes.Structure):
     _fields_ = [("pack", ctypes.c_int32),  # clm: 1 = documents concatenated and cut into full rows
                 # span: SDL_SPAN_*; policy 1: noise ids per 1000 ids of a row (the header's reserved[0], [1])
-                ("span_policy", ctypes.c_int32), ("span_noise_per_mille", ctypes.c_int32)]
+                ("span_policy", ctypes.c_int32), ("span_noise_per_mille", ctypes.c_int32),
+                # single-class / multi-label: 1 = two texts per example in one [CLS] A [SEP] B [SEP] row
+                ("pair", ctypes.c_int32)]
 
 
 class _ConfigTail(ctypes.Union):
@@ -53,7 +56,7 @@ class _ConfigTail(ctypes.Union):
     and span_noise_per_mille over its first two.  `reserved` stays the four-word view callers of
     this module have always had (pack was carved out of its first word, as mask_policy was carved
     out of the words before it): reserved[0] is pack, reserved[1] span_policy, reserved[2]
-    span_noise_per_mille."""
+    span_noise_per_mille, reserved[3] pair."""
     _anonymous_ = ("_w",)
     _fields_ = [("_w", _PackWord), ("reserved", ctypes.c_int32 * 4)]
 
@@ -205,6 +208,9 @@ def load(path=LIB_PATH):
     L.sdl_batch_release.restype = None
     L.sdl_process_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, ctypes.POINTER(DeviceRows)]
     L.sdl_process_device_labels.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, ctypes.POINTER(DeviceRows)]
+    L.sdl_batcher_push_pair.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(Batch)]
+    L.sdl_batcher_push_many_pairs.argtypes = [vp, vp, vp, sz, vp, vp, ctypes.POINTER(sz)]
+    L.sdl_process_device_pairs.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, ctypes.POINTER(DeviceRows)]
     L.sdl_device_to_host.argtypes = [vp, vp, vp, sz, vp]
     L.sdl_batch_position_ids.argtypes = [ctypes.POINTER(Batch)]
     L.sdl_batch_position_ids.restype = ctypes.POINTER(ctypes.c_int32)
@@ -247,7 +253,8 @@ def load(path=LIB_PATH):
     for name in ("sdl_batcher_create", "sdl_batcher_push", "sdl_batcher_push_many", "sdl_batcher_next",
                  "sdl_batcher_flush", "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device",
                  "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling",
-                 "sdl_stage_times"):
+                 "sdl_stage_times", "sdl_batcher_push_pair", "sdl_batcher_push_many_pairs",
+                 "sdl_process_device_pairs"):
         getattr(L, name).restype = i64
     _lib = L
     return L
