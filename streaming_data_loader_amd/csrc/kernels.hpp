@@ -304,6 +304,17 @@ struct RowOut {
     DirectDst direct;  // (k_rows) rows g < direct.cap go to the host batches; padding rows are skipped
 };
 
+// The lean rows kernels' own argument (k_rows_fast, rows_device.hpp "The lean rows"): what a row of
+// 16-byte aligned planes under the Philox contract reads, and nothing of RowParams / RowOut beside
+// it -- no host destinations, no f32 labels, no rng_mode 1 tables -- so that the row loop's
+// scalars fit the SGPRs.  launch_rows fills it.
+struct RowFast {
+    int32_t *input_ids, *attention_mask, *token_type_ids, *labels;  // token_type_ids may be null; labels: mlm / clm only
+    uint64_t seed, first_record;
+    int32_t S, B, chunk, mask_length, mask_id, n_pre, n_post, pad;
+    int32_t pre[MAX_FRAME], post[MAX_FRAME];
+};
+
 // Small calls: chunk scan + compaction + records + row scan + row map in one
 // single-workgroup launch (one segment, n_chunks <= SMALL_CHUNKS, R <= 8192).
 constexpr int64_t SMALL_CHUNKS = 64;
@@ -336,6 +347,17 @@ struct TokSrc {
     const uint32_t *chunk_off;  // [0 .. n_lists], chunk_off[n_lists] = the ids of chunks < n_lists
     int64_t n_lists;            // chunks scanned so far (pipelined segments: the segment's end)
     const uint32_t *row_chunk;  // row -> the chunk of its first id (k_row_map)
+};
+
+// k_rows_fast's one argument: the kernel reads it from the kernarg segment a row at a time
+// (rows_device.hpp "The lean rows"), so it is one struct at offset 0.
+struct RowsFastArgs {
+    RowFast F;
+    TokSrc tok;
+    const uint32_t *rec_tok, *rec_cnt, *row_off, *row_rec;
+    const uint32_t *rb;  // SegSel
+    int32_t k, last;
+    int64_t rows_cap;
 };
 
 // row -> record map (row_rec needs one word per row).  rc (optional): also row -> the chunk of its

@@ -688,6 +688,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MR >= 4 ? R
     }
 }
 
+// The lean rows (row_fast_one): k_rows' geometry and occupancy, one task body a kernel, RowsFastArgs
+// for RowParams and RowOut.  launch_rows picks it when S is a multiple of 4, nothing goes straight
+// to a host batch and the masks are the Philox contract's; every other call keeps k_rows.
+template <int MR, int TASK, bool LISTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MR >= 4 ? ROWS_WAVES4 : ROWS_WAVES, 8))) void k_rows_fast(
+    RowsFastArgs A) {
+    const int lane = lane_id();
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (the row's scalars live in SGPRs)
+    // row_span in 32 bits (rows are counted in row_off's words; launch_rows keeps rows_cap under
+    // 2^31): a wave writes two or three rows, and a 64-bit division costs it as much as half a row
+    const uint32_t g_lo = A.row_off[A.rb[A.k]], G = A.row_off[A.rb[A.k + 1]], step = gridDim.x * 4u;
+    uint32_t g_end = G;
+    if (A.last) {
+        const uint32_t B = (uint32_t)A.F.B, cap = (uint32_t)A.rows_cap;
+        uint32_t pad = (G + B - 1u) / B * B;
+        pad = pad > cap ? cap : pad;
+        g_end = pad > G ? pad : G;
+    }
+    // (A is the kernel's only argument: the kernarg segment starts with it)
+    const RowArgs a = (RowArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    for (uint32_t g = g_lo + blockIdx.x * 4u + wid; g < g_end; g += step)
+        row_fast_one<MR, TASK, LISTS>(a, g, G, lane);
+}
+
 // MLM rows under the BERT masking policies (MaskPolicy; row_policy_one): k_rows' geometry -- a
 // wave per row, four rows a block.  WHOLE: whole-word units (policy 2), with a wave's 256 MR
 // words of LDS for the units' sizes and picked flags; policy 1 is compiled without them.
@@ -1160,6 +1184,44 @@ constexpr int ROWS_GRID_CAP = 16384;
     // (rng_mode 1: the late pass scans 256 rows a block)
     const int64_t want_late = (rows_cap + 255) / 256;
     const unsigned grid_late = (unsigned)(want_late < 2048 ? want_late : 2048);
+    // The lean kernels (k_rows_fast): 16-byte aligned rows, device planes only, Philox masks.  mlm
+    // and clm write a label plane of the row's own width (label_width = S, so it is aligned with
+    // it); the label tasks write none here.
+    const bool label_task = P.task == 3 || P.task == 4;
+    const bool fast = (P.S & 3) == 0 && out.direct.cap == 0 && P.rng_mode == 0 && rows_cap < (int64_t(1) << 31) &&
+                      (label_task || ((P.task == 0 || P.task == 1) && out.labels && P.label_width == P.S));
+    if (fast) {
+        RowsFastArgs A{RowFast{out.input_ids, out.attention_mask, out.token_type_ids, label_task ? nullptr : out.labels,
+                               P.seed, P.first_record, P.S, P.B, P.chunk, P.mask_length, P.mask_id, P.n_pre, P.n_post,
+                               0, {}, {}},
+                       tok, rec_tok, rec_cnt, row_off, row_rec, sel.rb, sel.k, sel.last, rows_cap};
+        for (int q = 0; q < MAX_FRAME; ++q) {
+            A.F.pre[q] = P.pre[q];
+            A.F.post[q] = P.post[q];
+        }
+#define LAUNCH_FAST_L(MM, TT, LL)                                                                                       \
+    hipLaunchKernelGGL((k_rows_fast<MM, TT, LL>), dim3(grid), dim3(256), 0, st, A)
+#define LAUNCH_FAST(MM)                                                                                                 \
+    do {                                                                                                              \
+        if (tok.lists) {                                                                                              \
+            if (label_task) LAUNCH_FAST_L(MM, ROW_LABELS, true);                                                      \
+            else if (P.task == 0) LAUNCH_FAST_L(MM, ROW_MLM, true);                                                   \
+            else LAUNCH_FAST_L(MM, ROW_CLM, true);                                                                    \
+        } else {                                                                                                      \
+            if (label_task) LAUNCH_FAST_L(MM, ROW_LABELS, false);                                                     \
+            else if (P.task == 0) LAUNCH_FAST_L(MM, ROW_MLM, false);                                                  \
+            else LAUNCH_FAST_L(MM, ROW_CLM, false);                                                                   \
+        }                                                                                                             \
+    } while (0)
+        if (MR <= 1) LAUNCH_FAST(1);
+        else if (MR <= 2) LAUNCH_FAST(2);
+        else if (MR <= 4) LAUNCH_FAST(4);
+        else if (MR <= 8) LAUNCH_FAST(8);
+        else return hipErrorInvalidValue;
+#undef LAUNCH_FAST
+#undef LAUNCH_FAST_L
+        return hipGetLastError();
+    }
 #define LAUNCH_ROWS_L(MM, LL)                                                                                           \
     if (rm1) {                                                                                                        \
         hipLaunchKernelGGL((k_rows<MM, true, false, LL>), dim3(grid), dim3(256), 0, st, P, tok, rec_tok, rec_cnt,    \

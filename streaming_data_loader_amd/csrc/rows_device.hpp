@@ -582,6 +582,269 @@ __device__ __forceinline__ void row_one(const RowParams &P, const TokSrc &src,
 }
 
 // ---------------------------------------------------------------------------
+// The lean rows (k_rows_fast; DESIGN.md §3 "Lean rows").  k_rows is bound by scalar issue, not by
+// its bytes: row_one tests S, the label width, the host destination and the task again at every
+// plane store, and its row-invariant fields do not fit the SGPRs.  row_fast_one is the same row for
+// the calls launch_rows can promise more about -- S a multiple of 4 (every plane store one 16-byte
+// write), no host destination, the Philox contract, the task known at compile time:
+//   - a round of 256 positions is bounded once a row, and only the rounds that can pass S at all;
+//   - the token-type pointer is tested once a row;
+//   - the kernel's arguments are read where a row uses them (RowArgs), not kept across the row;
+//   - every id is loaded from a slot clamped into the row's own ids and selected afterwards, and
+//     the frame ids are selects: no exec-masked block a load.
+// Results are row_one's, bit for bit.
+// ---------------------------------------------------------------------------
+constexpr int ROW_MLM = 0, ROW_CLM = 1, ROW_LABELS = 2;  // multi-label / single-class: no label plane here
+
+// The kernel's argument where the hardware put it (the kernarg segment, constant address space).
+// Taken by value its row-invariant fields are all loaded before the row loop, and those that do
+// not fit the SGPRs are moved to VGPR lanes and back a dword an instruction; read through this
+// pointer, made opaque again (row_args_again) before each part of a row, a part's fields come
+// back by a few scalar loads of up to eight dwords each, from the scalar cache.
+typedef const __attribute__((address_space(4))) RowsFastArgs *RowArgs;
+__device__ __forceinline__ RowArgs row_args_again(RowArgs a) {
+    asm volatile("" : "+s"(a));
+    return a;
+}
+
+__device__ __forceinline__ void store4v(int32_t *p, int j0, int32_t a, int32_t b, int32_t c, int32_t d) {
+    typedef int32_t v4i __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(v4i{a, b, c, d}, reinterpret_cast<v4i *>(p + j0));
+}
+
+// row_ids for the lean rows.  Position j of the row holds an id when jlo <= j < jhi; lane positions
+// outside are clamped into that range before anything is addressed, so every load reads one of the
+// row's own ids (a row without ids loads nothing) and the clamped value is dropped by a select.
+template <int MR, bool LISTS>
+__device__ __forceinline__ RowIds<MR> row_ids_fast(RowArgs a, uint32_t c, uint32_t bnd, int64_t nl, uint32_t t0,
+                                                   uint32_t cnt, int64_t base, int l, int lane) {
+    const int n_pre = a->F.n_pre;
+    const int64_t rel0 = base > n_pre ? base - n_pre : 0;
+    const int64_t rel1 = base + l - n_pre < (int64_t)cnt ? base + l - n_pre : (int64_t)cnt;
+    const int jlo = (int)(rel0 + n_pre - base), jhi = (int)(rel1 + n_pre - base);
+    const uint32_t tb = t0 + (uint32_t)(base - n_pre);  // id index of position 0 (mod 2^32; exact on [jlo, jhi))
+    RowIds<MR> out;
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) out.v[m][w] = 0;
+    if (rel0 < rel1) {  // (wave-uniform) the row has ids: 0 <= jlo < jhi <= l
+        uint32_t t[MR][4];
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int j = 256 * m + 4 * lane + w;
+                const int jc = j < jlo ? jlo : j > jhi - 1 ? jhi - 1 : j;
+                t[m][w] = tb + (uint32_t)jc;
+            }
+        if constexpr (LISTS) {
+            const uint32_t t_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tb + (uint32_t)(jhi - 1)));
+            const uint16_t *__restrict__ lc = a->tok.lists + (int64_t)c * STAGE;
+            if ((uint32_t)__builtin_amdgcn_readlane((int)bnd, 63) > t_last) {
+                uint32_t q[MR][4];  // boundaries at or below the id: its chunk is c + q
+#pragma unroll
+                for (int m = 0; m < MR; ++m)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) q[m][w] = 0;
+#pragma unroll 1
+                for (int b = 1; b < 64; ++b) {
+                    const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)bnd, b);
+                    if (x > t_last) break;
+#pragma unroll
+                    for (int m = 0; m < MR; ++m)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) q[m][w] += t[m][w] >= x ? 1u : 0u;
+                }
+#pragma unroll
+                for (int m = 0; m < MR; ++m)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        // (q <= the boundaries walked: chunk c + q holds id t, at t - its offset)
+                        const uint32_t lo = (uint32_t)__shfl((int)bnd, (int)(q[m][w] & 63u));
+                        out.v[m][w] = (int32_t)lc[q[m][w] * (uint32_t)STAGE + (t[m][w] - lo)];
+                    }
+            } else {
+                // (a row past the 63 loaded boundaries: one position of every lane a step)
+                const uint32_t *const chunk_off = a->tok.chunk_off;
+                const uint16_t *const lists = a->tok.lists;
+#pragma unroll 1
+                for (int i = 0; i < 4 * MR; ++i) {
+                    uint32_t ti = 0;
+#pragma unroll
+                    for (int m = 0; m < MR; ++m)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) ti = i == 4 * m + w ? t[m][w] : ti;
+                    const int64_t cc = list_chunk_of(chunk_off, (int64_t)c, nl - 1, ti);
+                    const int32_t v = (int32_t)lists[list_slot(chunk_off, cc, ti)];
+#pragma unroll
+                    for (int m = 0; m < MR; ++m)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) out.v[m][w] = i == 4 * m + w ? v : out.v[m][w];
+                }
+            }
+        } else {
+            const uint32_t *const tok = a->tok.tok;
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) out.v[m][w] = (int32_t)tok[t[m][w]];
+        }
+    }
+    // before the ids the opening frame (lane 0's first positions: jlo <= n_pre <= MAX_FRAME), after
+    // them the closing one, past the row's l positions 0
+    a = row_args_again(a);
+    static_assert(MAX_FRAME == 4, "the frame selects below");
+    int32_t p0 = a->F.pre[0], p1 = a->F.pre[1], p2 = a->F.pre[2], p3 = a->F.pre[3];
+    int32_t q0 = a->F.post[0], q1 = a->F.post[1], q2 = a->F.post[2], q3 = a->F.post[3];
+    // (plain SGPR values to the optimizer: a select between loaded values is turned into a branch)
+    asm volatile("" : "+s"(p0), "+s"(p1), "+s"(p2), "+s"(p3), "+s"(q0), "+s"(q1), "+s"(q2), "+s"(q3));
+    // (every arm a value at hand, one select a statement: nested, the chain stays a branch)
+    auto frame4 = [](int k, int32_t x0, int32_t x1, int32_t x2, int32_t x3) {
+        int32_t x = x3;
+        x = k == 2 ? x2 : x;
+        x = k == 1 ? x1 : x;
+        x = k == 0 ? x0 : x;
+        return x;
+    };
+    const int post0 = (int)(base - n_pre - (int64_t)cnt);  // (+ j: the closing frame's index)
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int j = 256 * m + 4 * lane + w;
+            int32_t v = out.v[m][w];
+            if (m == 0) {
+                const int32_t f = frame4((int)base + j, p0, p1, p2, p3);
+                v = j < jlo ? f : v;
+            }
+            const int32_t f = frame4(post0 + j, q0, q1, q2, q3);
+            v = j >= jhi ? f : v;
+            out.v[m][w] = j < l ? v : 0;
+        }
+    return out;
+}
+
+// Round m of a lean row (positions 256 m + 4 lane + w) lies below S: rounds under MR / 2 always do
+// (MR is the power of two at or above ceil(S / 256)); S % 4 == 0, so a lane's four positions pass S
+// together.
+template <int MR>
+struct RowIn {
+    bool r[MR];
+};
+template <int MR>
+__device__ __forceinline__ RowIn<MR> row_in(int S, int lane) {
+    RowIn<MR> x;
+#pragma unroll
+    for (int m = 0; m < MR; ++m) x.r[m] = m < MR / 2 || 256 * m + 4 * lane < S;
+    return x;
+}
+
+// the planes of one lean row, every round's stores under its one bound; the token-type plane's
+// zeros behind one test of its pointer
+template <int MR, int TASK>
+__device__ __forceinline__ void row_fast_store(RowArgs a, uint32_t g, int lane, const int32_t (&v)[MR][4],
+                                               const int32_t (&am)[MR][4], const int32_t (&lab)[MR][4]) {
+    a = row_args_again(a);
+    const int S = a->F.S;
+    const RowIn<MR> in = row_in<MR>(S, lane);
+    const int64_t o = (int64_t)g * S;
+    int32_t *const ids_o = a->F.input_ids + o, *const am_o = a->F.attention_mask + o;
+    int32_t *const lb_o = TASK != ROW_LABELS ? a->F.labels + o : nullptr;
+    int32_t *const tt = a->F.token_type_ids;
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+        if (in.r[m]) {
+            const int j0 = 256 * m + 4 * lane;
+            store4v(ids_o, j0, v[m][0], v[m][1], v[m][2], v[m][3]);
+            store4v(am_o, j0, am[m][0], am[m][1], am[m][2], am[m][3]);
+            if constexpr (TASK != ROW_LABELS) store4v(lb_o, j0, lab[m][0], lab[m][1], lab[m][2], lab[m][3]);
+        }
+    if (tt) {
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+            if (in.r[m]) store4v(tt + o, 256 * m + 4 * lane, 0, 0, 0, 0);
+    }
+}
+
+// row_one for the lean kernels: row g of the call (a wave), g >= G a padding row of the last batch.
+template <int MR, int TASK, bool LISTS>
+__device__ __forceinline__ void row_fast_one(RowArgs a, uint32_t g, uint32_t G, int lane) {
+    int32_t v[MR][4], am[MR][4], lab[MR][4];
+    if (g >= G) {  // rows of the last batch nobody filled: initial values
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                v[m][w] = 0;
+                am[m][w] = 1;
+                lab[m][w] = -100;
+            }
+        row_fast_store<MR, TASK>(a, g, lane, v, am, lab);
+        return;
+    }
+    a = row_args_again(a);
+    const int S = a->F.S;
+    const int64_t nl = LISTS ? a->tok.n_lists : 0;
+    uint32_t c = 0, bnd = 0;  // (LISTS, as row_one) bnd(0) <= the row's first id < bnd(1)
+    if constexpr (LISTS) {
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)a->tok.row_chunk[g]);
+        bnd = a->tok.chunk_off[(int64_t)c + lane < nl ? (int64_t)c + lane : nl];
+    }
+    const uint32_t r = a->row_rec[g];
+    const uint32_t k = g - a->row_off[r];
+    const uint32_t cnt = a->rec_cnt[r];
+    const uint32_t t0 = a->rec_tok[r];
+    const int64_t n = (int64_t)cnt + a->F.n_pre + a->F.n_post;
+    const int64_t base = a->F.chunk ? (int64_t)k * S : 0;
+    const int l = (int)((n - base) < S ? (n - base) : S);
+    const RowIds<MR> ids = row_ids_fast<MR, LISTS>(a, c, bnd, nl, t0, cnt, base, l, lane);
+    const int32_t (&id)[MR][4] = ids.v;
+    // attention: 0 on [S-l, S) when l < S (reversed-range quirk, as row_one)
+    const int tail0 = l < S ? S - l : S;
+    if constexpr (TASK == ROW_MLM) {  // BertData::mask_batch
+        a = row_args_again(a);
+        const uint64_t rec = a->F.first_record + (uint64_t)r;
+        const uint64_t seed = a->F.seed;
+        const RowIn<MR> in = row_in<MR>(S, lane);
+        uint32_t key[MR][4];
+        bool sel[MR][4];
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            const uint4 x = philox4x32_10(make_uint4((uint32_t)(64 * m + lane), k, (uint32_t)rec, (uint32_t)(rec >> 32)),
+                                          (uint32_t)seed, (uint32_t)(seed >> 32));
+            key[m][0] = in.r[m] ? x.x : 0xFFFFFFFFu;
+            key[m][1] = in.r[m] ? x.y : 0xFFFFFFFFu;
+            key[m][2] = in.r[m] ? x.z : 0xFFFFFFFFu;
+            key[m][3] = in.r[m] ? x.w : 0xFFFFFFFFu;
+        }
+        select_k_smallest_interp<MR>(key, a->F.mask_length, S, sel);
+        a = row_args_again(a);
+        const int32_t mask_id = a->F.mask_id;
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const bool pick = sel[m][w] && id[m][w] != 0;
+                v[m][w] = pick ? mask_id : id[m][w];
+                lab[m][w] = pick ? id[m][w] : -100;
+                am[m][w] = 256 * m + 4 * lane + w >= tail0 ? 0 : 1;
+            }
+    } else {  // CLM: GptData::put_data, labels = row as i32 (no shift); the label tasks: BertData::put_data rows
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const bool tail = 256 * m + 4 * lane + w >= tail0;
+                v[m][w] = id[m][w];
+                am[m][w] = tail ? 0 : 1;
+                lab[m][w] = tail ? -100 : id[m][w];
+            }
+    }
+    row_fast_store<MR, TASK>(a, g, lane, v, am, lab);
+}
+
+// ---------------------------------------------------------------------------
 // The BERT masking policies (sdl_config.mask_policy 1 / 2; DESIGN.md §3 "Masking policies").
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t max_u32(uint32_t a, uint32_t b) { return a > b ? a : b; }
