@@ -32,8 +32,9 @@
 extern "C" {
 #endif
 
-/* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device and the three sentence-pair calls were
- * added without changing any existing call or struct (an additive change keeps the version). */
+/* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device, the three sentence-pair calls and the
+ * two pair-label accessors were added without changing any existing call or struct (an additive
+ * change keeps the version). */
 #define SDL_ABI_VERSION 9
 
 enum {
@@ -97,9 +98,11 @@ struct sdl_config {
                                              "Span policies").  0 = the reference's rule */
             int32_t span_noise_per_mille; /* policy 1: noise ids per 1000 ids of a row (T5: 150), 1..500;
                                              sdl_config_default leaves it 0, the caller states it */
-            int32_t pair;                 /* single-class / multi-label, WordPiece: 0 = one text per record;
-                                             1 = two texts per example in one [CLS] A [SEP] B [SEP] row
-                                             ("Sentence pairs" below).  Other values are refused */
+            int32_t pair;                 /* SDL_PAIR_*, WordPiece: 0 = one text per record; 1 = two texts per
+                                             example in one [CLS] A [SEP] B [SEP] row (single-class /
+                                             multi-label); 2..4 = that row under mlm with a BERT masking
+                                             policy and a pair label ("Sentence pairs" below).  Other
+                                             values are refused */
         };
     };
 };
@@ -194,7 +197,46 @@ typedef struct sdl_batcher sdl_batcher;
  * sdl_batcher_push_pair and sdl_batcher_push_many_pairs (sdl_batcher_next / _flush /
  * sdl_pickle_frames_device as they are); the unpaired calls return SDL_ERR_STATE on it and the
  * pair calls SDL_ERR_STATE on a handle with pair = 0.  sdl_json_to_frames and sdl_multi_create
- * return SDL_ERR_UNSUPPORTED. */
+ * return SDL_ERR_UNSUPPORTED.
+ *
+ * MLM rows and the NSP / SOP draw (pair = 2..4; task mlm, mask_policy 1 or 2, rng_mode 0, WordPiece,
+ * 3 <= sequence_length <= 2048): what BERT and ALBERT pre-train on.  A call's 2 n text ranges are
+ * n examples as above; `chunk` and `min_ids` are ignored, there is exactly one row per example, and
+ * every row carries a sentence-level pair label.  Example r of a call over n_pairs examples has
+ * global index rec = first_record + r and takes one Philox4x32-10 block, counter
+ * (0, 0x70000000, rec lo, rec hi), key (seed lo, seed hi), words x, y, z, w:
+ *     pair = 2 (SDL_PAIR_MLM)      first segment A_r, second B_r, pair label 0
+ *     pair = 3 (SDL_PAIR_MLM_NSP)  random = x >= 0x80000000 && n_pairs >= 2; if random the second
+ *                                  segment is B_s, s = j + (j >= r), j = umulhi(y, n_pairs - 1)
+ *                                  (uniform over the other examples of the same call), else B_r;
+ *                                  pair label = random (HF next_sentence_label: 0 = B continues A)
+ *     pair = 4 (SDL_PAIR_MLM_SOP)  swap = x >= 0x80000000; if swap the first segment is B_r and the
+ *                                  second A_r; pair label = swap (HF sentence_order_label)
+ * The NSP draw depends on how the stream is cut into calls: a call is one API call (the host
+ * calls hand a pair call to the device whole, never in parts), a foreign B comes from the same
+ * call, and a call of one pair is never random.  Keeping B_s out of A_r's document is the caller's
+ * job: put one document's pairs in different calls, or accept the noise as RoBERTa's ablation does.
+ * The unmasked row is the pair row above of the two chosen segments (kept lengths from the chosen
+ * sides' id counts, token types, the plain attention mask).  The masking is the mask_policy
+ * contract applied to that row as chunk 0 of record rec -- the row's own index, also when its
+ * second segment is foreign: candidates are the filled positions whose id is none of 0, mask_id,
+ * [CLS], [SEP]; k = min(mask_length, max(1, (l * mask_per_mille + 500) / 1000)) with
+ * l = k_a + k_b + 3, 0 without a candidate; keys, whole-word units, the 80/10/10 split and the
+ * random ids as for unpaired rows.  labels is [rows, S], -100 off the picks; the pair labels are an
+ * int32 plane of their own (sdl_device_pair_labels, sdl_batch_pair_labels).  Rows from *d_rows to
+ * the next multiple of B hold the unpaired mlm initial values (ids 0, attention 1, token types 0,
+ * labels -100) and pair label -100.  Label arguments of the pair calls are ignored.
+ * sdl_batcher_push_pair works under pair 2 and 4 and returns SDL_ERR_UNSUPPORTED under pair 3 (a
+ * call of one pair has nobody to draw from).  sdl_pickle_frames_device adds a fifth, flat key of
+ * the frame's filled rows after the four mlm keys: "next_sentence_label" under pair 2 and 3,
+ * "sentence_order_label" under pair 4. */
+enum {
+    SDL_PAIR_NONE = 0,    /* one text per record */
+    SDL_PAIR_ROWS = 1,    /* single-class / multi-label: [CLS] A [SEP] B [SEP] rows */
+    SDL_PAIR_MLM = 2,     /* mlm: pairs as given, pair label 0 everywhere */
+    SDL_PAIR_MLM_NSP = 3, /* mlm: next-sentence draws */
+    SDL_PAIR_MLM_SOP = 4  /* mlm: sentence-order draws */
+};
 
 /* Defaults of the reference masking cases (masking_cases.rs:38-94) for `task`:
  * B=4096 S=128 chunk=1 min_ids=64 mask 15%/103, span 16.0/2.0, 9 labels. */
@@ -242,6 +284,9 @@ void sdl_batch_release(sdl_batch *b);
 /* pack = 1: the batch's position_ids plane [batch_size, sequence_length] (owned like the other
  * planes); NULL for an unpacked batch. */
 const int32_t *sdl_batch_position_ids(const sdl_batch *b);
+/* pair = 2..4: the batch's pair labels [batch_size], the first `rows` filled, -100 above (owned like
+ * the other planes: valid until sdl_batch_release); NULL for any other batch. */
+const int32_t *sdl_batch_pair_labels(const sdl_batch *b);
 
 /* ---- Device-resident bulk path (the measured hot path) -------------------
  * Tokenize + label every record of a device-resident arena in one sequence of
@@ -305,6 +350,10 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
 int sdl_process_device_pairs(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len, const uint64_t *d_offsets,
                              uint64_t n_pairs, const uint32_t *d_labels, const uint64_t *d_label_offsets,
                              uint64_t first_record, void *stream, sdl_device_rows *out);
+/* pair = 2..4: the pair labels, device int32 [rows_capacity], of the handle's last
+ * sdl_process_device_pairs call (d_labels / d_label_offsets are ignored there; out->labels is the
+ * MLM label plane); NULL when pair is 0 or 1, or before the first call. */
+const int32_t *sdl_device_pair_labels(sdl_batcher *h);
 
 /* ---- Provider step: the JsonText filter on the device ----------------------
  * SourceFilter::JsonText over inflated JSON lines (gzip_file_provider.rs:30-50

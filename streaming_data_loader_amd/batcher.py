@@ -38,6 +38,10 @@ class Mask:
     # rule, 1 BERT's 80/10/10 by token, 2 by whole word; per mille of a row's filled positions
     mask_policy: int = 0
     mask_per_mille: int = 150
+    # sdl_config.pair (DESIGN.md §3 "Sentence pairs"): 0 one text per record; native.SDL_PAIR_MLM (2),
+    # SDL_PAIR_MLM_NSP (3), SDL_PAIR_MLM_SOP (4): [CLS] A [SEP] B [SEP] rows under mask_policy 1 / 2
+    # with a pair label (as given, next-sentence draws, sentence-order draws)
+    pair: int = 0
 
 
 @dataclass
@@ -164,6 +168,10 @@ class DataSet:
     labels: np.ndarray
     token_type_ids: Optional[np.ndarray] = None
     position_ids: Optional[np.ndarray] = None  # packed clm rows only (Gpt(pack=True))
+    # mlm sentence pairs only (Mask(pair=2..4)): int32 [B], -100 past `rows`, and the frame's key for
+    # them ("next_sentence_label" / "sentence_order_label")
+    pair_labels: Optional[np.ndarray] = None
+    pair_key: Optional[str] = None
 
     def to_dict(self):
         if self.kind == "bert-single":
@@ -173,8 +181,11 @@ class DataSet:
         if self.kind == "bert":
             # BertData.label is pushed per row: the list has `index` entries
             # (Vec<i32> for Mask, Vec<f32> for MultiLabel)
-            return {"input_ids": self.input_ids, "attention_mask": self.attention_mask,
-                    "token_type_ids": self.token_type_ids, "labels": self.labels[:self.rows]}
+            d = {"input_ids": self.input_ids, "attention_mask": self.attention_mask,
+                 "token_type_ids": self.token_type_ids, "labels": self.labels[:self.rows]}
+            if self.pair_labels is not None:  # one per filled row, like single-class `label`
+                d[self.pair_key or "next_sentence_label"] = self.pair_labels[:self.rows]
+            return d
         d = {"input_ids": self.input_ids, "attention_mask": self.attention_mask, "labels": self.labels}
         if self.position_ids is not None:
             d["position_ids"] = self.position_ids
@@ -202,6 +213,7 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
     if isinstance(dataset_config, Mask):
         c.mask_length, c.mask_id = dataset_config.mask_length, dataset_config.mask
         c.mask_policy, c.mask_per_mille = dataset_config.mask_policy, dataset_config.mask_per_mille
+        c.pair = int(dataset_config.pair)
     if isinstance(dataset_config, Gpt):
         c.pack = 1 if dataset_config.pack else 0
     if isinstance(dataset_config, Span):
@@ -241,7 +253,7 @@ class _BatchOwner:
             pass
 
 
-def _dataset_from(b: native.Batch, kind: str) -> DataSet:
+def _dataset_from(b: native.Batch, kind: str, pair_key: Optional[str] = None) -> DataSet:
     """Zero-copy: the DataSet's arrays are views of the batch's pinned planes
     (the D2H wrote them there directly)."""
     b = native.Batch.from_buffer_copy(b)  # callers reuse their sdl_batch struct
@@ -256,10 +268,12 @@ def _dataset_from(b: native.Batch, kind: str) -> DataSet:
     i32 = (ctypes.c_int32, np.int32)
     labels = arr(b.labels_f32, B, LW, ctypes.c_float, np.float32) if bool(b.labels_f32) else arr(b.labels, B, LW, *i32)
     pos = native.load().sdl_batch_position_ids(ctypes.byref(b))
+    plab = native.load().sdl_batch_pair_labels(ctypes.byref(b))
     return DataSet(kind=kind, rows=b.rows, input_ids=arr(b.input_ids, B, S, *i32),
                    attention_mask=arr(b.attention_mask, B, S, *i32), labels=labels,
                    token_type_ids=arr(b.token_type_ids, B, S, *i32) if bool(b.token_type_ids) else None,
-                   position_ids=arr(pos, B, S, *i32) if bool(pos) else None)
+                   position_ids=arr(pos, B, S, *i32) if bool(pos) else None,
+                   pair_labels=arr(plab, 1, B, *i32)[0] if bool(plab) else None, pair_key=pair_key if bool(plab) else None)
 
 
 # ---- SimpleTransport (models/simple_transport.rs, simple_label.rs) ----------------
@@ -320,6 +334,9 @@ class _NativeBatcher(Batcher):
         native.track(self)
         self.batch_config = batch_config
         self.dataset_config = dataset_config
+        # mlm sentence pairs: the key DataSet.to_dict() files the pair labels under (the frames' fifth key)
+        self.pair_key = None if c.pair < native.SDL_PAIR_MLM else \
+            "sentence_order_label" if c.pair == native.SDL_PAIR_MLM_SOP else "next_sentence_label"
 
     @classmethod
     def from_config(cls, cfg: TrainingConfig, chunk: bool = True):
@@ -340,14 +357,15 @@ class _NativeBatcher(Batcher):
         got = native.check(native.load().sdl_batcher_push(self._h, raw, len(raw),
                                                           None if lab is None else lab.ctypes.data,
                                                           0 if lab is None else lab.size, ctypes.byref(b)))
-        return _dataset_from(b, self.kind) if got else None
+        return _dataset_from(b, self.kind, self.pair_key) if got else None
 
-    def _push_pair(self, a: bytes, b: bytes, labels) -> Optional[DataSet]:
+    def _push_pair(self, a: bytes, b: bytes, labels=None) -> Optional[DataSet]:
         out = native.Batch()
-        lab = np.ascontiguousarray(labels, np.uint32)
-        got = native.check(native.load().sdl_batcher_push_pair(self._h, a, len(a), b, len(b), lab.ctypes.data,
+        lab = np.ascontiguousarray([] if labels is None else labels, np.uint32)
+        got = native.check(native.load().sdl_batcher_push_pair(self._h, a, len(a), b, len(b),
+                                                               lab.ctypes.data if lab.size else None,
                                                                lab.size, ctypes.byref(out)))
-        return _dataset_from(out, self.kind) if got else None
+        return _dataset_from(out, self.kind, self.pair_key) if got else None
 
     def push_arena(self, arena, offsets, labels=None, label_offsets=None, pairs=False):
         """sdl_batcher_push_many over a host arena (uint8) + uint64 offsets
@@ -370,13 +388,13 @@ class _NativeBatcher(Batcher):
         out = []
         b = native.Batch()
         while native.check(native.load().sdl_batcher_next(self._h, ctypes.byref(b))):
-            out.append(_dataset_from(b, self.kind))
+            out.append(_dataset_from(b, self.kind, self.pair_key))
         return out
 
     def get_working_batch(self) -> Optional[DataSet]:
         b = native.Batch()
         got = native.check(native.load().sdl_batcher_flush(self._h, ctypes.byref(b)))
-        return _dataset_from(b, self.kind) if got else None
+        return _dataset_from(b, self.kind, self.pair_key) if got else None
 
 
 class GenTokenizer(_NativeBatcher):
@@ -395,6 +413,21 @@ class GenTokenizer(_NativeBatcher):
         np.cumsum(np.fromiter(map(len, blobs), np.uint64, len(blobs)), out=offs[1:])
         arena = np.frombuffer(b"".join(blobs), np.uint8)  # the C side stages (and pads) it
         return self.push_arena(arena, offs)
+
+    def create_sync_batch_pair(self, a, b) -> Optional[DataSet]:
+        """MLM sentence pairs (Mask(pair=2 or 4)): one example of two texts, sdl_batcher_push_pair.
+        Next-sentence draws (pair=3) need a call of several pairs: create_sync_batches_pairs."""
+        def raw(t):
+            return t.encode("utf-8") if isinstance(t, str) else bytes(t)
+        return self._push_pair(raw(a), raw(b))
+
+    def create_sync_batches_pairs(self, pairs):
+        """MLM sentence pairs (Mask(pair=2..4)): (A, B) examples in one device pass -- one call for the
+        next-sentence draw, which picks a foreign B among this call's pairs; returns the batches
+        emitted, in order, their pair labels in DataSet.pair_labels."""
+        from .device import arena_from_pairs
+        arena, offs = arena_from_pairs(pairs)
+        return self.push_arena(arena, offs, pairs=True)
 
 
 class SimpleBatcher(_NativeBatcher):

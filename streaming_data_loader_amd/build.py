@@ -21,10 +21,10 @@ BUILD = os.path.join(REPO, "build", "sdl")
 LIB = os.path.join(PKG, "libsdl_batcher.so")
 ARCH = os.environ.get("SDL_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pair.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
+SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
            "assets.cpp", "sdl_batcher.cpp", "provider_json.cpp", "provider_gzip.cpp", "provider_zstd.cpp", "transport.cpp"]
 HEADERS = ["common.hpp", "device_util.hpp", "kernels.hpp", "tok_device.hpp", "assets.hpp", "json.hpp", "unigram.hpp", "handle.hpp",
-           "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "span_noise.hpp", "pack_queue.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
+           "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "span_noise.hpp", "pair_draw.hpp", "pack_queue.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(REPO, "include"), "-I", CSRC]
 

@@ -154,6 +154,9 @@ struct HostBatch {
     int rows = 0;
     int B, S, LW;
     bool tt_is_pos = false;  // pack = 1 (clm): the fourth plane holds position_ids, not token types
+    // pair 2..4 (mlm): the pair label of every row, [B] (plain host memory: the cadence loop writes
+    // it from the call's pair-label plane); empty otherwise
+    std::vector<int32_t> pair_lab;
     static size_t block_bytes(int B, int S, int LW, bool with_tt) {
         return 4 * (size_t)B * ((size_t)S * (with_tt ? 3 : 2) + (size_t)LW);
     }
@@ -188,6 +191,7 @@ struct HostBatch {
         if (tt) std::fill(tt + r0 * S, tt + r1 * S, 0);  // (token types and position_ids alike)
         if (lab) std::fill(lab + r0 * LW, lab + r1 * LW, -100);
         if (f32) std::fill(f32 + r0 * LW, f32 + r1 * LW, 0.f);
+        if (!pair_lab.empty()) std::fill(pair_lab.begin() + (long)r0, pair_lab.end(), -100);
     }
     ~HostBatch() { pool->put(BatchPool::Block{block, dev}); }
 };
@@ -463,14 +467,17 @@ struct sdl_batcher {
     // HostBatch.tt); the public token_type_ids stays NULL
     bool pack() const { return cfg.pack == 1; }
     bool plane4() const { return with_tt() || pack(); }
-    // sdl_config.pair = 1: a call's 2 n text ranges are n examples of two texts, one row each (pair.hip)
-    bool pair() const { return cfg.pair == 1; }
+    // sdl_config.pair != 0: a call's 2 n text ranges are n examples of two texts, one row each
+    // (pair = 1: pair.hip, the label tasks; pair 2..4: pair_mlm.hip, mlm with a drawn pair label)
+    bool pair() const { return cfg.pair != 0; }
+    bool pair_mlm() const { return cfg.pair >= SDL_PAIR_MLM; }
 
     std::shared_ptr<BatchPool> pool;
     HostBatch *new_batch() {
         if (!pool) pool = std::make_shared<BatchPool>(HostBatch::block_bytes(P.B, P.S, P.label_width, plane4()));
         HostBatch *b = new HostBatch(pool, P.B, P.S, P.label_width, plane4(), multi());
         b->tt_is_pos = pack();
+        if (pair_mlm()) b->pair_lab.assign((size_t)P.B, -100);
         return b;
     }
 
@@ -487,9 +494,12 @@ struct sdl_batcher {
     PackParams pack_params(int64_t R, int64_t rows_cap);
     void run_pack(int64_t R, int64_t rows_cap, hipStream_t st);
     void run_pack_flush(hipStream_t st);
-    DevBuf<uint32_t> pair_rb;  // pair = 1: the label kernels' record bounds {0, n_pairs}
-    void run_pair(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st,
-                  const uint32_t *d_labels, const uint64_t *d_label_off);
+    DevBuf<uint32_t> pair_rb;  // pair != 0: the one segment's record bounds {0, n_pairs}
+    DevBuf<int32_t> o_pair_lab;  // pair 2..4: the pair label of every row of the last call, grown with the row planes
+    bool pair_lab_ran = false;   // ... written by a call (sdl_device_pair_labels is NULL before)
+    PinBuf<int32_t> pin_pair_lab;  // host path: the call's pair labels beside its row offsets
+    void run_pair(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, uint64_t first_record,
+                  hipStream_t st, const uint32_t *d_labels, const uint64_t *d_label_off);
     int64_t rows_capacity(int64_t N, int64_t R) const;
     void run_device(const uint8_t *d_text, int64_t N, const uint64_t *d_off, int64_t R, uint64_t first_record,
                     hipStream_t st, const uint32_t *d_labels = nullptr, const uint64_t *d_label_off = nullptr);

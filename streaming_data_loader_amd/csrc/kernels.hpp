@@ -450,6 +450,27 @@ struct PairParams {
 };
 hipError_t launch_rows_pair(const PairParams &q, hipStream_t st);
 
+// pair_mlm.hip: the same row under the MLM task with a BERT masking policy applied and a sentence-level
+// label drawn (sdl_config.pair 2..4, DESIGN.md §3 "Sentence pairs": NSP / SOP), after launch_records
+// over the 2 * n_pairs text ranges.  A struct of its own again: k_rows_pair and k_rows_policy compile
+// to what they were.
+struct PairMlmParams {
+    const uint16_t *lists;                    // as PairParams
+    const uint32_t *chunk_off;
+    const uint64_t *off;
+    int64_t n_lists;
+    const uint32_t *rec_tok, *rec_cnt;
+    int64_t n_pairs, rows_end;                // rows filled; rows written (n_pairs rounded up to B, within the planes)
+    uint64_t seed, first_record;              // the Philox key; row r is record first_record + r for its draw and its masks
+    int32_t S, cls, sep, mode;                // mode: sdl_config.pair (PAIR_MODE_MLM .. PAIR_MODE_MLM_SOP, pair_draw.hpp)
+    int32_t mask_length, mask_id;             // the row's cap of predictions; the [MASK] id
+    MaskPolicy mp;                            // policy 1 / 2, per mille, vocabulary size, continuation bitmap
+    int32_t *ids, *am, *tt, *lab;             // planes [rows_end .., S]: every column of every row < rows_end is written
+    int32_t *pair_lab;                        // [rows_end ..]: the pair label of rows < n_pairs, -100 above
+    uint32_t *row_off, *row_rec, *rb;         // out, as PairParams
+};
+hipError_t launch_rows_pair_mlm(const PairMlmParams &q, hipStream_t st);
+
 // rng_mode 1 masks (pipeline.hip): the rows rand_pre_slot names (chunk 0 of every record, chunk 1
 // of long ones) from (seed, first_record + r, chunk) alone -- launched beside the tokenizer: swap
 // indices (lane per row) into jbuf [2 R, S], then the mask bits into P.mask_bits0 slots
@@ -508,10 +529,10 @@ struct FramePlane {
     uint64_t frame_stride;    // source elements per frame (B * width; flat: B)
     uint64_t off_full;   // frame offset of row 0 (just past the key segment), full frames
     uint64_t off_last;   // the same in the last frame
-    uint8_t key[24];
+    uint8_t key[32];     // 'X' + u32 length + the name (the longest: "sentence_order_label") (+ "](")
 };
 struct FrameParams {
-    FramePlane plane[4];
+    FramePlane plane[5];        // (the fifth: the pair label of mlm sentence pairs)
     uint8_t *out;
     uint64_t frame_bytes;       // every frame but the last
     uint64_t last_frame_bytes;

@@ -99,11 +99,44 @@ void sdl_batcher::run_pack_flush(hipStream_t st) {
 }
 
 // pair = 1: the call's rows from rec_tok / rec_cnt of its 2 n text ranges (after launch_records), one
-// launch for the three planes, then the task's label kernel over n rows -- no host synchronisation
-void sdl_batcher::run_pair(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st,
-                           const uint32_t *d_labels, const uint64_t *d_label_off) {
+// launch for the three planes, then the task's label kernel over n rows -- no host synchronisation;
+// pair 2..4 (mlm): one launch for the four planes and the pair labels (pair_mlm.hip)
+void sdl_batcher::run_pair(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, uint64_t first_record,
+                           hipStream_t st, const uint32_t *d_labels, const uint64_t *d_label_off) {
     const int64_t n = R / 2;
     pair_rb.ensure(2);
+    if (pair_mlm()) {
+        o_pair_lab.ensure((size_t)std::max<int64_t>(rows_cap, 1));
+        PairMlmParams m{};
+        m.lists = reinterpret_cast<const uint16_t *>(tokc.p);
+        m.chunk_off = chunk_off.p;
+        m.off = d_off;
+        m.n_lists = n_chunks;
+        m.rec_tok = rec_tok.p;
+        m.rec_cnt = rec_cnt.p;
+        m.n_pairs = n;
+        m.rows_end = std::min<int64_t>((n + P.B - 1) / P.B * P.B, rows_cap);
+        m.seed = P.seed;
+        m.first_record = first_record;
+        m.S = P.S;
+        m.cls = tok.tpl_cls;
+        m.sep = tok.tpl_sep;
+        m.mode = cfg.pair;
+        m.mask_length = P.mask_length;
+        m.mask_id = P.mask_id;
+        m.mp = mpol;
+        m.ids = o_ids.p;
+        m.am = o_am.p;
+        m.tt = o_tt.p;
+        m.lab = o_lab.p;
+        m.pair_lab = o_pair_lab.p;
+        m.row_off = row_off.p;
+        m.row_rec = row_rec.p;
+        m.rb = pair_rb.p;
+        HIP_TRY(launch_rows_pair_mlm(m, st));
+        pair_lab_ran = true;
+        return;
+    }
     PairParams q{};
     q.lists = reinterpret_cast<const uint16_t *>(tokc.p);
     q.chunk_off = chunk_off.p;
@@ -317,7 +350,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
         }
         if (pair()) {  // a row per pair of text ranges instead of row scan, row map and k_rows
             mark(6);
-            run_pair(R, rows_cap, n_chunks, d_off, s, d_labels, d_label_off);
+            run_pair(R, rows_cap, n_chunks, d_off, first_record, s, d_labels, d_label_off);
             return;
         }
         // (segment k's rows read lists and offsets of chunks < cz only: all written by now)
@@ -604,6 +637,11 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
         HIP_TRY(hipMemcpyAsync(pin_u32.p, row_off.p, sizeof(uint32_t) * (size_t)(E + 1), hipMemcpyDeviceToHost,
                                stream));
         pin_u32.p[E + 1] = pin_u32.p[E + 2] = 0;
+        if (pair_mlm()) {  // the pair labels ride the same synchronisation (row g of the call is pair g)
+            pin_pair_lab.ensure((size_t)E + 1);
+            HIP_TRY(hipMemcpyAsync(pin_pair_lab.p, o_pair_lab.p, sizeof(int32_t) * (size_t)E, hipMemcpyDeviceToHost,
+                                   stream));
+        }
         if (span()) HIP_TRY(hipMemcpyAsync(pin_u32.p + E + 1, span_err.p, 4, hipMemcpyDeviceToHost, stream));
         if (dt.kind == TOK_UNIGRAM)
             HIP_TRY(hipMemcpyAsync(pin_u32.p + E + 2, uni_err.p, 4, hipMemcpyDeviceToHost, stream));
@@ -638,6 +676,7 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
                 if (!segs.empty() && segs.back().b == b && segs.back().g0 + segs.back().n == g) ++segs.back().n;
                 else segs.push_back(Seg{b, (uint32_t)b->rows, g, 1u});
             }
+            if (!b->pair_lab.empty()) b->pair_lab[(size_t)b->rows] = pin_pair_lab.p[g];
             b->rows++;
             if (b->rows == P.B) {
                 store.push_back(spare ? spare : new_batch());
@@ -751,9 +790,24 @@ int check_config(const sdl_config *cfg) {
         cfg->task != SDL_TASK_SPAN && cfg->task != SDL_TASK_SINGLE_CLASS)
         return fail(SDL_ERR_UNSUPPORTED, "unknown task");
     // (sentence pairs first: a task or tokenizer they are not built for is named as that)
-    if (cfg->pair != 0 && cfg->pair != 1)
-        return fail(SDL_ERR_ARG, "pair must be 0 (one text per record) or 1 (sentence pairs); other values are reserved");
-    if (cfg->pair == 1) {
+    if (cfg->pair < SDL_PAIR_NONE || cfg->pair > SDL_PAIR_MLM_SOP)
+        return fail(SDL_ERR_ARG, "pair must be 0 (one text per record), 1 (sentence pairs) or 2..4 (mlm sentence pairs); "
+                                 "other values are reserved");
+    if (cfg->pair >= SDL_PAIR_MLM) {
+        if (cfg->task != SDL_TASK_MLM)
+            return fail(SDL_ERR_ARG, "pair = 2..4 (mlm sentence pairs, NSP / SOP draws) apply to the MLM task only");
+        if (cfg->mask_policy == SDL_MASK_REFERENCE)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pair = 2..4 with mask_policy 0: the reference's rule masks [CLS] / [SEP] and defines nothing "
+                        "for pairs; use mask_policy 1 or 2");
+        if (cfg->rng_mode == 1)
+            return fail(SDL_ERR_UNSUPPORTED, "pair = 2..4 need rng_mode 0: the draw and the masks are on the Philox contract");
+        if (cfg->sequence_length < 3)
+            return fail(SDL_ERR_ARG, "pair = 2..4 need sequence_length >= 3: [CLS] A [SEP] B [SEP]");
+        if (cfg->sequence_length > 2048)
+            return fail(SDL_ERR_ARG, "pair = 2..4 need sequence_length <= 2048 (the masking kernels' limit)");
+    }
+    if (cfg->pair == SDL_PAIR_ROWS) {
         if (cfg->task != SDL_TASK_SINGLE_CLASS && cfg->task != SDL_TASK_MULTI_LABEL)
             return fail(SDL_ERR_UNSUPPORTED,
                         "pair = 1 with task mlm, clm or span: sentence pairs are built for the single-class and "
@@ -965,6 +1019,10 @@ void fill_row_params(sdl_batcher *h) {
         P.chunk = 0;
         P.min_ids = 0;
     }
+    if (cfg->pair >= SDL_PAIR_MLM) {  // mlm sentence pairs: one row per pair, `chunk` and `min_ids` ignored
+        P.chunk = 0;
+        P.min_ids = 0;
+    }
     P.seed = cfg->seed;
     P.rng_mode = cfg->rng_mode;
     h->mpol = MaskPolicy{cfg->mask_policy, cfg->mask_per_mille, (uint32_t)t.pieces.size(), 0u, nullptr};
@@ -1109,6 +1167,11 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
         h->cfg = *cfg;
         h->device = cfg->device;
         load_tokenizer(tokenizer_path, data_dir ? std::string(data_dir) : default_data_dir(), h->tok);
+        // (mlm sentence pairs first, so that the refusal names them also under mask_policy 2)
+        if (cfg->pair >= SDL_PAIR_MLM && (h->tok.kind != TOK_WORDPIECE || h->tok.cls_id < 0 || h->tok.sep_id < 0))
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pair = 2..4 with a byte-level BPE or Unigram tokenizer: mlm sentence pairs need a WordPiece "
+                        "tokenizer with [CLS] and [SEP] ids");
         if (cfg->mask_policy == SDL_MASK_BERT_WHOLE_WORD && h->tok.kind != TOK_WORDPIECE)
             return fail(SDL_ERR_UNSUPPORTED,
                         "mask_policy 2 (SDL_MASK_BERT_WHOLE_WORD) needs a WordPiece tokenizer: whole words are "
@@ -1198,6 +1261,10 @@ int sdl_batcher_push_pair(sdl_batcher *h, const uint8_t *a, size_t len_a, const 
                           const uint32_t *labels, size_t n_labels, sdl_batch *out) {
     if (!h || (!a && len_a) || (!b && len_b) || (!labels && n_labels)) return fail(SDL_ERR_ARG, "null argument");
     if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push_pair needs a handle created with pair = 1");
+    if (h->cfg.pair == SDL_PAIR_MLM_NSP)
+        return fail(SDL_ERR_UNSUPPORTED,
+                    "sdl_batcher_push_pair under pair = 3: a call of one pair has nobody to draw a next sentence "
+                    "from; use sdl_batcher_push_many_pairs");
     if (h->multi()) {
         if (int rc = check_labels(h, labels, n_labels)) return rc;
     }
@@ -1275,6 +1342,12 @@ const int32_t *sdl_batch_position_ids(const sdl_batch *b) {
     return hb->tt_is_pos ? hb->tt : nullptr;
 }
 
+const int32_t *sdl_batch_pair_labels(const sdl_batch *b) {
+    if (!b || !b->owner_) return nullptr;
+    const HostBatch *hb = static_cast<const HostBatch *>(b->owner_);
+    return hb->pair_lab.empty() ? nullptr : hb->pair_lab.data();
+}
+
 int sdl_process_device(sdl_batcher *h, const uint8_t *d_text, uint64_t text_len, const uint64_t *d_offsets,
                        uint64_t n_records, uint64_t first_record, void *stream, sdl_device_rows *out) {
     return sdl_process_device_labels(h, d_text, text_len, d_offsets, n_records, nullptr, nullptr, first_record, stream,
@@ -1318,6 +1391,10 @@ int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out) {
 }
 
 const int32_t *sdl_device_position_ids(sdl_batcher *h) { return h && h->pack() && h->pk_ran ? h->o_tt.p : nullptr; }
+
+const int32_t *sdl_device_pair_labels(sdl_batcher *h) {
+    return h && h->pair_mlm() && h->pair_lab_ran ? h->o_pair_lab.p : nullptr;
+}
 
 int sdl_tokenizer_info_get(const char *tokenizer_path, const char *data_dir, sdl_tokenizer_info *out) {
     if (!tokenizer_path || !out) return fail(SDL_ERR_ARG, "null argument");
@@ -1397,6 +1474,10 @@ int sdl_multi_create(const sdl_config *cfg, const char *tokenizer_path, const ch
     if (!cfg || !devices || !out || n_devices == 0) return fail(SDL_ERR_ARG, "null argument or no devices");
     if (cfg->pair == 1)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_multi_create with pair = 1: sentence pairs are not sharded over several handles");
+    if (cfg->pair >= SDL_PAIR_MLM && cfg->pair <= SDL_PAIR_MLM_SOP)
+        return fail(SDL_ERR_UNSUPPORTED,
+                    "sdl_multi_create with pair = 2..4: sentence pairs are not sharded over several handles (a next-"
+                    "sentence draw is over one call's pairs)");
     std::unique_ptr<sdl_multi> m(new sdl_multi());
     m->next_record = cfg->first_record;
     for (uint32_t k = 0; k < n_devices; ++k) {

@@ -51,7 +51,7 @@ int sdl_pickle_frames_device(sdl_batcher *h, const sdl_device_rows *rows, uint64
     if (n_frames * B > rows->rows_capacity)
         return fail(SDL_ERR_ARG, "n_rows exceeds the rows the device planes hold");
     const bool bert = task == SDL_TASK_MLM || task == SDL_TASK_MULTI_LABEL || task == SDL_TASK_SINGLE_CLASS;
-    FramePlaneDesc d[4];
+    FramePlaneDesc d[5];
     int np = 0;
     d[np++] = {"input_ids", rows->input_ids, (uint32_t)S, false, false, false};
     d[np++] = {"attention_mask", rows->attention_mask, (uint32_t)S, false, false, false};
@@ -62,6 +62,10 @@ int sdl_pickle_frames_device(sdl_batcher *h, const sdl_device_rows *rows, uint64
         d[np++] = {"label", rows->labels, 1, false, true, true};
     else
         d[np++] = {"labels", rows->labels, (uint32_t)LW, false, bert, false};
+    // mlm sentence pairs: the pair labels of the frame's filled rows, one flat list (like `label`)
+    if (h->pair_mlm())
+        d[np++] = {h->cfg.pair == SDL_PAIR_MLM_SOP ? "sentence_order_label" : "next_sentence_label",
+                   h->pair_lab_ran ? h->o_pair_lab.p : nullptr, 1, false, true, true};
     for (int p = 0; p < np; ++p)
         if (!d[p].src && n_frames) return fail(SDL_ERR_ARG, std::string("device plane missing: ") + d[p].name);
     return guarded(SDL_ERR_ARG, SDL_ERR_ARG, [&]() -> int {
@@ -69,7 +73,7 @@ int sdl_pickle_frames_device(sdl_batcher *h, const sdl_device_rows *rows, uint64
         fp.n_planes = np;
         fp.B = (uint32_t)B;
         fp.n_frames = n_frames;
-        uint32_t full_rows[4], last_rows[4];
+        uint32_t full_rows[5], last_rows[5];
         const bool partial = n_frames && n_frames * B > n_rows;
         for (int p = 0; p < np; ++p) {
             FramePlane &P = fp.plane[p];
@@ -131,6 +135,8 @@ int sdl_json_to_frames(sdl_batcher *h, const uint8_t *jsonl, uint64_t len, uint6
                        sdl_frame_sink sink, void *user, sdl_json_frames_stats *stats) {
     if (!h || (!jsonl && len)) return fail(SDL_ERR_ARG, "null argument");
     const int task = h->cfg.task;
+    if (h->pair_mlm())
+        return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: pair = 2..4 is not supported (one text member a line)");
     if (h->pair())
         return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: pair = 1 is not supported (one text member a line)");
     if (task != SDL_TASK_MLM && task != SDL_TASK_CLM && task != SDL_TASK_SPAN)

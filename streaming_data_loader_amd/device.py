@@ -22,9 +22,10 @@ class _CudaView:
 
 
 class DeviceResult:
-    def __init__(self, handle, rows_struct, n_records, S, B=None, device=0, stream=0, pos_ptr=None):
+    def __init__(self, handle, rows_struct, n_records, S, B=None, device=0, stream=0, pos_ptr=None, pair_ptr=None):
         self.h = handle
         self.pos_ptr = pos_ptr  # packed clm rows: the position_ids plane (sdl_device_position_ids)
+        self.pair_ptr = pair_ptr  # mlm sentence pairs: the pair labels (sdl_device_pair_labels)
         self.r = rows_struct
         self.n_records = n_records
         self.S = S
@@ -87,6 +88,16 @@ class DeviceResult:
         n = self.rows() if n_rows is None else n_rows
         a = np.zeros((n, self.S), np.int32)
         return native.d2h(self.h, a, self.pos_ptr, a.nbytes)
+
+    def pair_labels(self, n_rows=None):
+        """MLM sentence pairs (DeviceBatcher(pair=2..4)): the pair label of every row as numpy int32
+        [n] -- next_sentence_label under pair 2 / 3, sentence_order_label under pair 4, -100 on the
+        rows past the call's pairs; None otherwise."""
+        if not self.pair_ptr:
+            return None
+        n = self.rows() if n_rows is None else n_rows
+        a = np.zeros(n, np.int32)
+        return native.d2h(self.h, a, self.pair_ptr, a.nbytes)
 
     def tensors(self, n_rows=None, device=None):
         """The planes as zero-copy torch tensors on the device, keyed as the
@@ -164,7 +175,7 @@ class DeviceBatcher:
         c.rng_mode = rng_mode
         c.mask_policy, c.mask_per_mille = mask_policy, mask_per_mille
         c.pack = int(pack)
-        c.pair = int(pair)  # single-class / multi-label: sentence pairs (process_pairs)
+        c.pair = int(pair)  # native.SDL_PAIR_*: sentence pairs (process_pairs); True = 1, 2..4 under mlm
         c.span_policy, c.span_noise_per_mille = span_policy, span_noise_per_mille
         c.avg_span_gap, c.avg_span_size = avg_span_gap, avg_span_size
         if min_ids is not None:
@@ -225,14 +236,15 @@ class DeviceBatcher:
                       first_record=0, stream=0):
         """Sentence pairs (pair=True; sdl_process_device_pairs): A_r is text range 2r and B_r range
         2r + 1 of the device arena (2 n_pairs + 1 offsets, arena_from_pairs); labels per pair
-        (n_pairs + 1 label offsets).  One [CLS] A [SEP] B [SEP] row per pair."""
+        (n_pairs + 1 label offsets; ignored under mlm).  One [CLS] A [SEP] B [SEP] row per pair;
+        under pair=2..4 (mlm) the result's pair_labels() holds each row's drawn label."""
         out = native.DeviceRows()
         native.check(native.load().sdl_process_device_pairs(
             self._h, ctypes.c_void_p(text_ptr), text_len, ctypes.c_void_p(offsets_ptr), n_pairs,
             ctypes.c_void_p(labels_ptr or None), ctypes.c_void_p(label_offsets_ptr or None), first_record,
             ctypes.c_void_p(stream or None), ctypes.byref(out)))
         return DeviceResult(self._h, out, n_pairs, self.cfg.sequence_length, self.cfg.batch_size, self.cfg.device,
-                            stream)
+                            stream, pair_ptr=native.load().sdl_device_pair_labels(self._h))
 
     def json_text(self, jsonl_ptr, jsonl_len, stream=0):
         """The provider's JsonText filter on the device (sdl_json_text_device):

@@ -22,6 +22,9 @@ SDL_TASK_MLM, SDL_TASK_CLM, SDL_TASK_SPAN, SDL_TASK_MULTI_LABEL, SDL_TASK_SINGLE
 SDL_MASK_REFERENCE, SDL_MASK_BERT, SDL_MASK_BERT_WHOLE_WORD = 0, 1, 2
 # sdl_config.span_policy: the reference's rule, T5's random_spans_noise_mask
 SDL_SPAN_REFERENCE, SDL_SPAN_T5 = 0, 1
+# sdl_config.pair: one text per record, pair rows (single-class / multi-label), then mlm pair rows
+# with the pair label 0, a next-sentence draw, a sentence-order draw
+SDL_PAIR_NONE, SDL_PAIR_ROWS, SDL_PAIR_MLM, SDL_PAIR_MLM_NSP, SDL_PAIR_MLM_SOP = 0, 1, 2, 3, 4
 
 # every symbol include/sdl_batcher.h declares
 EXPORTS = [
@@ -29,6 +32,7 @@ EXPORTS = [
     "sdl_batcher_push_many", "sdl_batcher_next", "sdl_batcher_flush", "sdl_batch_release",
     "sdl_batcher_push_pair", "sdl_batcher_push_many_pairs", "sdl_process_device_pairs",
     "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids",
+    "sdl_batch_pair_labels", "sdl_device_pair_labels",
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
     "sdl_gzip_inflate_device", "sdl_gzip_inflate_first_device", "sdl_gzip_split_members", "sdl_build_id",
@@ -47,7 +51,8 @@ class _PackWord(ctypes.Structure):
     _fields_ = [("pack", ctypes.c_int32),  # clm: 1 = documents concatenated and cut into full rows
                 # span: SDL_SPAN_*; policy 1: noise ids per 1000 ids of a row (the header's reserved[0], [1])
                 ("span_policy", ctypes.c_int32), ("span_noise_per_mille", ctypes.c_int32),
-                # single-class / multi-label: 1 = two texts per example in one [CLS] A [SEP] B [SEP] row
+                # SDL_PAIR_*: 1 = two texts per example in one [CLS] A [SEP] B [SEP] row (single-class /
+                # multi-label); 2..4 = that row under mlm with a masking policy and a pair label
                 ("pair", ctypes.c_int32)]
 
 
@@ -218,6 +223,10 @@ def load(path=LIB_PATH):
     L.sdl_pack_flush_device.restype = i64
     L.sdl_device_position_ids.argtypes = [vp]
     L.sdl_device_position_ids.restype = vp
+    L.sdl_batch_pair_labels.argtypes = [ctypes.POINTER(Batch)]
+    L.sdl_batch_pair_labels.restype = ctypes.POINTER(ctypes.c_int32)
+    L.sdl_device_pair_labels.argtypes = [vp]
+    L.sdl_device_pair_labels.restype = vp
     L.sdl_json_text_device.argtypes = [vp, vp, u64, vp, ctypes.POINTER(JsonText)]
     L.sdl_pickle_frames_device.argtypes = [vp, ctypes.POINTER(DeviceRows), u64, i64, vp, ctypes.POINTER(Frames)]
     L.sdl_json_to_frames.argtypes = [vp, vp, u64, u64, i64, FRAME_SINK, vp, ctypes.POINTER(JsonFramesStats)]
