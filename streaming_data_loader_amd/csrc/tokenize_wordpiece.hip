@@ -53,12 +53,15 @@
 //   5. staged ids (LDS, indexed by piece byte position: a piece never has
 //      more ids than bytes) are compacted into this chunk's slice of `tokc`
 //      as a packed u16 list (STAGE slots a chunk), which the rows kernel reads
-//      as it lies (pipeline.hip, list_index.hpp).  Lane t packs its own 16
-//      slots: a slot holds an id where a piece starts (the piece-start mask
-//      in its registers) unless the exception bitmap says otherwise -- a piece
-//      with more than one id, or none (wp_pack.hpp) -- and its list position
-//      is a wave sum plus a popcount.  Each record boundary's local id offset
-//      comes from the same sums, fetched from the owning lane by a shuffle.
+//      as it lies (pipeline.hip, list_index.hpp).  A slot holds an id where a
+//      piece starts (the piece-start mask in the lane's registers) unless the
+//      exception bitmap says otherwise -- a piece with more than one id, or
+//      none (wp_pack.hpp).  A chunk without an exception bit (nearly every
+//      chunk of in-vocabulary text) gathers its list through the piece
+//      descriptors of step 3: entry e is the id staged at piece e's slot.  In
+//      a chunk with exceptions lane t packs its own 16 slots, a slot's list
+//      position a wave sum plus a popcount.  Each record boundary's local id
+//      offset comes from the same sums, fetched from the owning lane by a shuffle.
 #include "common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
@@ -479,7 +482,7 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     uint32_t *__restrict__ rec_local, int64_t c_begin) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[WIN];
     __shared__ uint32_t s_rbits[RBITS_WORDS + 1];
-    __shared__ uint16_t s_pieces[CHUNK];   // (pos - c0) | kind << 12
+    __shared__ __attribute__((aligned(16))) uint16_t s_pieces[CHUNK];   // (pos - c0) | kind << 12
     __shared__ __attribute__((aligned(16))) uint16_t s_stage[STAGE];  // ids staged at their piece's byte position
     // per-byte class overrides of the rare pass (step 2); from step 4 on its first words are the
     // exception bitmap of the stage slots (wp_pack.hpp) and, behind it, the stop and
@@ -1166,12 +1169,16 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     PHASE_STAMP(7);
 
     // ---- 5. compact ids into this chunk's tokc slice ------------------------------
-    // Lane t packs the ids of its own stage slots [16t, 16t + 16) -- lanes 0-7 also the tail
-    // slots [CHUNK + 16t, ...), which only the chunk's last word reaches.  A slot holds an id
-    // where a piece starts (pmask, still in registers) or the exception bitmap says otherwise
-    // (wp_pack.hpp); a slot's list position is a wave sum plus a popcount.  No walk over the
-    // piece list, no per-piece counts.
-    const uint32_t vmain = pmask ^ wp_bits16(s_vx, 16 * tid);
+    // Lane t owns the stage slots [16t, 16t + 16) -- lanes 0-7 also the tail slots
+    // [CHUNK + 16t, ...), which only the chunk's last word reaches.  A slot holds an id where a
+    // piece starts (pmask, still in registers) or the exception bitmap says otherwise
+    // (wp_pack.hpp); a slot's list position is a wave sum plus a popcount, and the record
+    // boundaries' offsets come from the same sums in every case below.  (a) A chunk without an
+    // exception bit is gathered through the piece list; (b) one with exceptions is packed slot
+    // by slot in LDS (pack16) and copied out; (c) one with exceptions and more ids than the
+    // window holds stores straight to its slice.
+    const uint32_t vx16 = wp_bits16(s_vx, 16 * tid);
+    const uint32_t vmain = pmask ^ vx16;
     const uint32_t vtail = tid < WP_TAIL_LANES ? wp_bits16(s_vx, CHUNK + 16 * tid) : 0u;
     uint32_t tot2;
     const uint32_t ex2 = block_excl_sum<TOK_THREADS>(wp_lane_counts(vmain, vtail), &tot2, s_scratch);
@@ -1188,7 +1195,34 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(WP_
     // be in the memory-side cache then (mlm rows 0.324 ms after non-temporal
     // stores, 0.270 after plain ones; the tokenizer itself 1.118 -> 1.116 ms;
     // profiles/r07/lists).
-    if (total <= (uint32_t)(WIN / 2)) {
+    // A further id adds to `total` and a piece without an id takes from it, so a chunk whose total
+    // differs from its piece count has exceptions: one scalar compare sends it on, and only a
+    // chunk with total == np pays the wave vote over the bitmap.
+    if (total == (uint32_t)np && !__any((vx16 | vtail) != 0u)) {
+        // (a) no exception bit in the chunk: every piece has exactly one id, in the stage slot
+        // of its first byte, so list entry e is s_stage[s_pieces[e] & 0xFFF] and total == np.
+        // The lane of entries [8k, 8k + 8) reads their descriptors with one 16-B read, their
+        // ids from the slots the descriptors name, and stores 16 bytes to the slice.  An entry
+        // at or past np holds a stale descriptor: wp_pair_slots keeps its slot inside the stage,
+        // and what the last store leaves past `total` is unspecified, as below.  A chunk of more
+        // ids than the window holds comes here too.
+        for (uint32_t e = 8u * (uint32_t)tid; e < total; e += 8u * TOK_THREADS) {
+            const uint4 d = *reinterpret_cast<const uint4 *>(s_pieces + e);
+            const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
+            uint32_t o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t s2 = wp_pair_slots(dw[j]);  // (entries past np: stale, kept inside the stage)
+                o[j] = (uint32_t)s_stage[s2 & 0xFFFFu] | ((uint32_t)s_stage[s2 >> 16] << 16);
+            }
+            u32x4 v;
+            v.x = o[0];
+            v.y = o[1];
+            v.z = o[2];
+            v.w = o[3];
+            *reinterpret_cast<u32x4 *>(dst + e) = v;
+        }
+    } else if (total <= (uint32_t)(WIN / 2)) {
         lds_u16 *packed = (lds_u16 *)s_win;
         // 16 unconditional 2-B stores a lane, no loop and no branch: a slot without an id goes
         // to a per-lane dump slot in the pending list's space (dead now)

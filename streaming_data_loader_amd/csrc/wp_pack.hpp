@@ -1,7 +1,7 @@
 // Mask arithmetic of the WordPiece chunk kernel's id compaction (tokenize_wordpiece.hip, step 5):
 // which stage slots hold an id, where each lands in the chunk's packed list, and the id offset of
 // a record boundary.  Includes nothing from HIP, so a host program can call it
-// (tests/test_wp_pack.py).
+// (tests/test_wp_pack.py, tests/test_wp_pack_piece.py).
 //
 // A chunk stages its ids in WP_SLOTS slots, a piece's ids from the slot of its first byte on.
 // Lane t of the wave owns the main slots [16t, 16t + 16); lanes 0-7 also own the tail slots
@@ -9,6 +9,9 @@
 // an id if its bit is set in `piece starts ^ exceptions`: a piece that finished with one id (nearly
 // all) needs no exception, one with n > 1 ids sets the bits of its slots 1 .. n-1, one with none
 // sets (so clears) its own.  The list is the valid main slots in order, then the valid tail slots.
+// (No text reaches the n == 0 case today: a piece starts at a char whose class is not "removed",
+// and such a char's normalized form is never empty, so every finished piece has at least one id
+// -- [UNK] if nothing else.  The bit's arithmetic is kept whole and checked on the host.)
 #pragma once
 #include <cstdint>
 
@@ -71,5 +74,14 @@ WP_PACK_FN uint32_t wp_pos(uint32_t base, uint32_t valid, int i) {
 // ids of the pieces that start before it.
 WP_PACK_FN int wp_boundary_lane(int rel) { return rel >> 4; }
 WP_PACK_FN uint32_t wp_boundary_offset(uint32_t base, uint32_t valid, int rel) { return wp_pos(base, valid, rel & 15); }
+
+// ---- an exception-free chunk, by piece ----------------------------------------------------------
+// The chunk's piece list holds a descriptor a piece in list order, the stage slot of the piece's
+// first byte in bits 0-11.  In a chunk without an exception bit piece e's one id is list entry
+// e, so the list is a gather through the descriptors, with no walk over the 1,152 slots.  Two
+// descriptors a dword -> their slots, each kept below WP_MAIN: an entry at or past the piece
+// count holds a stale descriptor (any 12 bits), whose id nobody reads but whose slot must still
+// lie inside the stage.
+WP_PACK_FN uint32_t wp_pair_slots(uint32_t desc2) { return desc2 & (0x00010001u * (uint32_t)(WP_MAIN - 1)); }
 
 }  // namespace sdl
