@@ -90,7 +90,9 @@ struct sdl_config {
                                 mask_length stays the row's maximum.  Ignored under policy 0 */
     int32_t pack;            /* CLM, byte-level BPE: 0 = GenTokenizer's rows (every record cut into its own
                                 rows); 1 = documents concatenated with the end-of-text id and the stream
-                                cut into full rows ("Packed rows" below).  Carved out of reserved[4] */
+                                cut into full rows ("Packed rows" below).  Carved out of reserved[4].
+                                MLM, WordPiece, mask_policy 1 / 2: 1 = [CLS] ids [SEP] documents
+                                concatenated, cut into full rows and masked ("Packed mlm rows" there) */
     union {                  /* the last three words under two views: a zeroed config is the reference's */
         int32_t reserved[3];
         struct {
@@ -176,7 +178,26 @@ typedef struct sdl_batcher sdl_batcher;
  * last -- and returns 0 once no filled row is left.  sdl_batch.token_type_ids stays NULL.
  * sdl_multi_*: each shard's handle packs its own records, so packed rows, unlike unpacked ones,
  * are not the rows one handle gives over the whole stream.  sdl_json_to_frames returns
- * SDL_ERR_UNSUPPORTED; sdl_pickle_frames_device frames a packed call's three reference keys. */
+ * SDL_ERR_UNSUPPORTED; sdl_pickle_frames_device frames a packed call's three reference keys.
+ *
+ * Packed mlm rows (pack = 1 with task mlm, a WordPiece tokenizer, mask_policy 1 or 2, rng_mode 0,
+ * pair 0, 3 <= S <= 2048): HF run_mlm.py's group_texts and RoBERTa's FULL-SENTENCES.  Record r is
+ * kept when n_r >= 1 and n_r + 2 >= min_ids, and the stream is
+ *     carry ++ concat over kept r of ([CLS] ++ t_r ++ [SEP])
+ * with the tokenizer's own [CLS] / [SEP] ids; the carry is unmasked.  Rows, carry, flush row,
+ * padding rows and position_ids (restarting at each row start and at each document's [CLS]) are
+ * as above; token_type_ids is 0 everywhere and stays non-NULL; input_ids / labels are the
+ * "Masking policies" contract applied to the row as chunk 0 of record q with l = S (the flush
+ * row: l = c), q being the number of packed rows the handle emitted before it, flush rows
+ * included -- so the rows of any sequence of calls over a record list equal the rows of one call,
+ * bit for bit, and first_record is unused.  Candidates exclude 0, mask_id, [CLS] and [SEP]; a row
+ * that begins inside a word starts a whole-word unit at column 0.  d_record_rows[r] = n_r + 2 or
+ * 0; rows_capacity = (ids + 2 R + S - 1) / S + 1 rounded up to B.  sdl_batcher_create refuses
+ * mask_policy 0, pair != 0 and S outside 3..2048 (SDL_ERR_ARG), rng_mode 1 and a tokenizer that is
+ * not WordPiece (SDL_ERR_UNSUPPORTED); sdl_json_to_frames and sdl_multi_create return
+ * SDL_ERR_UNSUPPORTED (shards would reuse one index range: give each handle its own seed);
+ * sdl_pickle_frames_device frames the four mlm keys over the packed planes, no position_ids key.
+ * sdl_batch.token_type_ids is one read-only zero plane shared by the handle's batches. */
 
 /* ---- Sentence pairs (sdl_config.pair = 1; tasks single-class and multi-label, WordPiece) ----
  * No counterpart in the reference (SimpleData.alt_text is tokenized and dropped, dataset.rs:47):

@@ -42,6 +42,9 @@ class Mask:
     # SDL_PAIR_MLM_NSP (3), SDL_PAIR_MLM_SOP (4): [CLS] A [SEP] B [SEP] rows under mask_policy 1 / 2
     # with a pair label (as given, next-sentence draws, sentence-order draws)
     pair: int = 0
+    # sdl_config.pack (DESIGN.md §3 "Packed rows"): [CLS] ids [SEP] documents concatenated, the stream
+    # cut into full rows and each row masked (mask_policy 1 / 2), with a position_ids plane
+    pack: bool = False
 
 
 @dataclass
@@ -167,7 +170,7 @@ class DataSet:
     attention_mask: np.ndarray
     labels: np.ndarray
     token_type_ids: Optional[np.ndarray] = None
-    position_ids: Optional[np.ndarray] = None  # packed clm rows only (Gpt(pack=True))
+    position_ids: Optional[np.ndarray] = None  # packed rows only (Gpt(pack=True), Mask(pack=True))
     # mlm sentence pairs only (Mask(pair=2..4)): int32 [B], -100 past `rows`, and the frame's key for
     # them ("next_sentence_label" / "sentence_order_label")
     pair_labels: Optional[np.ndarray] = None
@@ -185,6 +188,8 @@ class DataSet:
                  "token_type_ids": self.token_type_ids, "labels": self.labels[:self.rows]}
             if self.pair_labels is not None:  # one per filled row, like single-class `label`
                 d[self.pair_key or "next_sentence_label"] = self.pair_labels[:self.rows]
+            if self.position_ids is not None:  # packed mlm rows
+                d["position_ids"] = self.position_ids
             return d
         d = {"input_ids": self.input_ids, "attention_mask": self.attention_mask, "labels": self.labels}
         if self.position_ids is not None:
@@ -214,7 +219,7 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
         c.mask_length, c.mask_id = dataset_config.mask_length, dataset_config.mask
         c.mask_policy, c.mask_per_mille = dataset_config.mask_policy, dataset_config.mask_per_mille
         c.pair = int(dataset_config.pair)
-    if isinstance(dataset_config, Gpt):
+    if isinstance(dataset_config, (Gpt, Mask)):
         c.pack = 1 if dataset_config.pack else 0
     if isinstance(dataset_config, Span):
         c.avg_span_gap, c.avg_span_size = dataset_config.avg_span_gap, dataset_config.avg_span_size

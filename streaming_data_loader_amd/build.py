@@ -21,12 +21,15 @@ BUILD = os.path.join(REPO, "build", "sdl")
 LIB = os.path.join(PKG, "libsdl_batcher.so")
 ARCH = os.environ.get("SDL_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
+SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pack_mlm.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
            "assets.cpp", "sdl_batcher.cpp", "provider_json.cpp", "provider_gzip.cpp", "provider_zstd.cpp", "transport.cpp"]
 HEADERS = ["common.hpp", "device_util.hpp", "kernels.hpp", "tok_device.hpp", "assets.hpp", "json.hpp", "unigram.hpp", "handle.hpp",
-           "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "span_noise.hpp", "pair_draw.hpp", "pack_queue.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
+           "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "span_noise.hpp", "pair_draw.hpp", "pack_queue.hpp", "pack_search.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(REPO, "include"), "-I", CSRC]
+# per-source flags on top of FLAGS: newer kernels are compiled without packed fp32 instructions
+# (the older sources keep the flags, and so the machine code, they had)
+EXTRA_FLAGS = {"pack_mlm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -55,6 +58,7 @@ def source_hash(defines=()):
         with open(path, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS[:-4] + [f"-D{d}" for d in defines]).encode())
+    h.update(repr(sorted(EXTRA_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -156,7 +160,8 @@ def build(verbose=False, force=False, jobs=4, defines=(), lib=None, build_dir=No
         objs.append(obj)
         if force or not _newer(obj, [src] + hdrs):
             lang = ["-x", "hip"] if s.endswith(".hip") else []
-            todo.append([hipcc] + FLAGS + [f"-D{d}" for d in defines] + lang + ["-c", src, "-o", obj])
+            todo.append([hipcc] + FLAGS + EXTRA_FLAGS.get(s, []) + [f"-D{d}" for d in defines] + lang +
+                        ["-c", src, "-o", obj])
     # the build id: a one-line translation unit regenerated per link
     idsrc = os.path.join(bdir, "build_id.cpp")
     with open(idsrc, "w") as f:
@@ -214,6 +219,15 @@ def build_span_ablations(levels=(1, 2)):
     SDL_LIB=... tools/span_policy_bench.py (where the policy's rows stage spends its time)."""
     return [build(defines=(f"SDL_SPAN_T5_ABLATE={n}",), lib=os.path.join(REPO, "var", f"span_abl{n}", "libsdl_batcher.so"),
                   build_dir=os.path.join(REPO, "build", f"span_abl{n}")) for n in levels]
+
+
+def build_pack_mlm_ablations(levels=(1, 2)):
+    """Diagnostic builds of k_pack_mlm_rows (SDL_PACK_MLM_ABLATE: 1 no pick and no draws, 2 no list reads
+    either: the record searches and the stores are left; their rows are not the contract's) ->
+    var/pack_mlm_abl{n}/libsdl_batcher.so, for SDL_LIB=... tools/pack_mlm_bench.py (DESIGN.md §4 "Packed
+    mlm rows": where the packed rows stage spends its time)."""
+    return [build(defines=(f"SDL_PACK_MLM_ABLATE={n}",), lib=os.path.join(REPO, "var", f"pack_mlm_abl{n}", "libsdl_batcher.so"),
+                  build_dir=os.path.join(REPO, "build", f"pack_mlm_abl{n}")) for n in levels]
 
 
 if __name__ == "__main__":

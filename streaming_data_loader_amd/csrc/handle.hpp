@@ -153,7 +153,9 @@ struct HostBatch {
     float *f32 = nullptr;  // MultiLabel: [B, number_labels]
     int rows = 0;
     int B, S, LW;
-    bool tt_is_pos = false;  // pack = 1 (clm): the fourth plane holds position_ids, not token types
+    bool tt_is_pos = false;  // pack = 1: the fourth plane holds position_ids, not token types
+    // packed mlm: the token types handed out (all 0, one read-only plane shared by the handle's batches)
+    std::shared_ptr<std::vector<int32_t>> zero_tt;
     // pair 2..4 (mlm): the pair label of every row, [B] (plain host memory: the cadence loop writes
     // it from the call's pair-label plane); empty otherwise
     std::vector<int32_t> pair_lab;
@@ -466,6 +468,10 @@ struct sdl_batcher {
     // position_ids travel through the token-type plumbing clm does not use (o_tt, RowSeg.tt,
     // HostBatch.tt); the public token_type_ids stays NULL
     bool pack() const { return cfg.pack == 1; }
+    // ... and under the MLM task (pack_mlm.hip) the position_ids take the same route, so the token
+    // types -- all 0 in a packed row -- are a plane of their own on the device (o_tt0) and one
+    // shared zero plane for the host batches (zero_tt): sdl_batch and sdl_device_rows keep their sizes
+    bool pack_mlm() const { return pack() && P.task == SDL_TASK_MLM; }
     bool plane4() const { return with_tt() || pack(); }
     // sdl_config.pair != 0: a call's 2 n text ranges are n examples of two texts, one row each
     // (pair = 1: pair.hip, the label tasks; pair 2..4: pair_mlm.hip, mlm with a drawn pair label)
@@ -477,13 +483,23 @@ struct sdl_batcher {
         if (!pool) pool = std::make_shared<BatchPool>(HostBatch::block_bytes(P.B, P.S, P.label_width, plane4()));
         HostBatch *b = new HostBatch(pool, P.B, P.S, P.label_width, plane4(), multi());
         b->tt_is_pos = pack();
+        if (pack_mlm()) {
+            if (!zero_tt) zero_tt = std::make_shared<std::vector<int32_t>>((size_t)P.B * (size_t)P.S, 0);
+            b->zero_tt = zero_tt;
+        }
         if (pair_mlm()) b->pair_lab.assign((size_t)P.B, -100);
         return b;
     }
 
     // pack = 1: the carry between calls, double buffered (ids and position_ids, S each per half),
-    // and pk_meta = {rows of the last call, length of half 0, length of half 1}; the host only
-    // knows which half is current -- it flips per call, the lengths stay on the device
+    // and pk_meta = {rows of the last call, length of half 0, length of half 1, -, and (mlm) the
+    // packed rows emitted so far as two 64-bit counters, half 0 and half 1}; the host only
+    // knows which half is current -- it flips per call, the lengths and counters stay on the device
+    static constexpr size_t PK_META_WORDS = 8;
+    std::shared_ptr<std::vector<int32_t>> zero_tt;  // packed mlm: the host batches' token_type_ids
+    DevBuf<int32_t> o_tt0;                          // packed mlm: the device rows' token_type_ids
+    PackMlmParams pack_mlm_params(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off);
+    void run_pack_mlm(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st);
     DevBuf<int32_t> pk_carry;
     DevBuf<uint32_t> pk_meta, pk_off;
     int pk_cur = 0;

@@ -425,12 +425,45 @@ struct PackParams {
     int32_t *ids, *am, *lab, *pos;            // planes [rows_cap, S]
     uint32_t *d_rows;                         // out: rows emitted
 };
-// rec_len and pk_off[0] = the carry length: then launch_exclusive_scan(rec_len, pk_off, R, tmp, st, pk_off)
-hipError_t launch_pack_lengths(const PackParams &q, hipStream_t st);
+// rec_len and pk_off[0] = the carry length: then launch_exclusive_scan(rec_len, pk_off, R, tmp, st, pk_off).
+// add: the framing ids a kept record brings (1: clm's eos; 2: packed mlm's [CLS] and [SEP]); the
+// kernel reads rec_cnt, rec_len, pk_off, R, min_ids and carry_len only
+hipError_t launch_pack_lengths(const PackParams &q, hipStream_t st, int add = 1);
 // the four planes (gather over the flat output index), then the new carry, its length and d_rows
 hipError_t launch_pack_rows(const PackParams &q, hipStream_t st);
 // the carry as one last row (0 rows when it is empty), rows < B of the planes; the new carry is empty
 hipError_t launch_pack_flush(const PackParams &q, hipStream_t st);
+
+// pack_mlm.hip: MLM rows packed from the stream of [CLS] ids [SEP] documents with a BERT masking policy
+// applied to every full row (sdl_config.pack = 1 under the MLM task, DESIGN.md §3 "Packed rows"),
+// after launch_records, launch_pack_lengths(.., 2) and the seeded scan into pk_off.  A struct of its
+// own again: k_pack_gather and k_rows_policy compile to what they were.
+struct PackMlmParams {
+    const uint16_t *lists;                    // the WordPiece chunk lists as the tokenizer wrote them (TokSrc.lists):
+    const uint32_t *chunk_off;                //   no dense copy of the ids
+    const uint64_t *off;                      //   [R + 1] record byte ranges: the chunks a record's ids lie in
+    int64_t n_lists;                          //   chunks of the call
+    const uint32_t *rec_tok, *rec_cnt;        // each record's first id / id count
+    const uint32_t *pk_off;                   // [R + 1]: where record r starts in the call's stream; [R] = its length
+    int64_t R, rows_cap;                      // rows_cap * S < 2^32
+    uint64_t seed;                            // the Philox key; a row's masks are those of chunk 0 of record row_cnt + g
+    int32_t S, B, cls, sep;                   // the tokenizer's own [CLS] / [SEP] ids, not RowParams.pre / post
+    int32_t mask_length, mask_id;             // the row's cap of predictions; the [MASK] id
+    MaskPolicy mp;                            // policy 1 / 2, per mille, vocabulary size, continuation bitmap
+    const int32_t *carry_ids, *carry_pos;     // the carry the last call left (< S unmasked ids and their position_ids)
+    const uint32_t *carry_len;
+    int32_t *new_ids, *new_pos;               // the other half of the double buffer: this call's carry
+    uint32_t *new_len;
+    const uint64_t *row_cnt;                  // packed rows the handle emitted before this call ...
+    uint64_t *new_row_cnt;                    // ... and after it (the other half, like the carry length)
+    int32_t *ids, *am, *tt, *lab, *pos;       // planes [rows_cap, S]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// the five planes (a wave per packed row: gathered from the lists and masked), then the new carry,
+// its length, the row counter and d_rows
+hipError_t launch_pack_mlm_rows(const PackMlmParams &q, hipStream_t st);
+// the carry as one last masked row (0 rows when it is empty), rows < B of the planes; the new carry is empty
+hipError_t launch_pack_mlm_flush(const PackMlmParams &q, hipStream_t st);
 
 // pair.hip: one [CLS] A [SEP] B [SEP] row per example of two texts (sdl_config.pair = 1, DESIGN.md §3
 // "Sentence pairs"), after launch_records over the 2 * n_pairs text ranges.  A struct of its own, not

@@ -15,31 +15,21 @@
 // reason.
 #include "device_util.hpp"
 #include "kernels.hpp"
+#include "pack_search.hpp"
 
 namespace sdl {
 
-// Per record: its packed length (the ids and one trailing eos, or 0 when dropped) into rec_len
-// (sdl_device_rows.d_record_rows); thread 0 seeds the scan with the carry length.
+// Per record: its packed length (the ids and ADD framing ids -- clm: one trailing eos; mlm: [CLS]
+// and [SEP] -- or 0 when dropped) into rec_len (sdl_device_rows.d_record_rows); thread 0 seeds the
+// scan with the carry length.
+template <uint32_t ADD>
 __global__ __launch_bounds__(256) void k_pack_lengths(PackParams q) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) q.pk_off[0] = *q.carry_len;
     for (int64_t r = i; r < q.R; r += (int64_t)gridDim.x * 256) {
         const uint32_t n = q.rec_cnt[r];
-        q.rec_len[r] = n >= 1u && n + 1u >= (uint32_t)(q.min_ids > 0 ? q.min_ids : 0) ? n + 1u : 0u;
+        q.rec_len[r] = n >= 1u && n + ADD >= (uint32_t)(q.min_ids > 0 ? q.min_ids : 0) ? n + ADD : 0u;
     }
-}
-
-// The record holding stream position p, c0 <= p < L: the last r in [lo, hi] with pk_off[r] <= p
-// (records of length 0 share their successor's offset and are never the answer).  The caller
-// guarantees pk_off[lo] <= p.
-__device__ __forceinline__ uint32_t pack_record_of(const uint32_t *__restrict__ pk_off, uint32_t lo, uint32_t hi,
-                                                   uint32_t p) {
-    while (lo < hi) {
-        const uint32_t m = lo + (hi - lo + 1u) / 2u;
-        if (pk_off[m] <= p) lo = m;
-        else hi = m - 1u;
-    }
-    return lo;
 }
 
 struct PackElem {
@@ -64,20 +54,6 @@ __device__ __forceinline__ void pack_store4(int32_t *__restrict__ o, uint32_t p,
         for (int w = 0; w < 4; ++w)
             if (p + (uint32_t)w < end) o[p + w] = v[w];
     }
-}
-
-// The same for a caller whose answer lies near lo (a lane after its wave's search, or after its
-// own last position): a galloping search, one or two loads where a binary search over every
-// record takes log2 R dependent ones.
-__device__ __forceinline__ uint32_t pack_record_near(const uint32_t *__restrict__ pk_off, uint32_t lo, uint32_t last,
-                                                     uint32_t p) {
-    uint32_t step = 1u;
-    while (lo + step <= last && pk_off[lo + step] <= p) {
-        lo += step;
-        step <<= 1;
-    }
-    const uint32_t hi = lo + step - 1u < last ? lo + step - 1u : last;
-    return pack_record_of(pk_off, lo, hi, p);
 }
 
 // The four planes over the flat output index.  A wave takes PACK_WAVE_POS consecutive positions
@@ -218,10 +194,11 @@ __global__ __launch_bounds__(256) void k_pack_flush(PackParams q) {
     }
 }
 
-hipError_t launch_pack_lengths(const PackParams &q, hipStream_t st) {
+hipError_t launch_pack_lengths(const PackParams &q, hipStream_t st, int add) {
     const int64_t want = (q.R + 255) / 256;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want < 1024 ? want : 1024);
-    hipLaunchKernelGGL(k_pack_lengths, dim3(grid), dim3(256), 0, st, q);
+    if (add == 2) hipLaunchKernelGGL(k_pack_lengths<2u>, dim3(grid), dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(k_pack_lengths<1u>, dim3(grid), dim3(256), 0, st, q);
     return hipGetLastError();
 }
 

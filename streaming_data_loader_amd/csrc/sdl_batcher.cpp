@@ -83,6 +83,56 @@ void sdl_batcher::run_pack(int64_t R, int64_t rows_cap, hipStream_t st) {
     pk_cur ^= 1;
     pk_ran = true;
 }
+// packed mlm: the same carry buffers, the row counter beside the carry lengths, the chunk lists in
+// the place of the dense ids and the token types in a plane of their own
+PackMlmParams sdl_batcher::pack_mlm_params(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off) {
+    const PackParams c = pack_params(R, rows_cap);
+    uint64_t *cnt = reinterpret_cast<uint64_t *>(pk_meta.p + 4);
+    PackMlmParams q{};
+    q.lists = reinterpret_cast<const uint16_t *>(tokc.p);
+    q.chunk_off = chunk_off.p;
+    q.off = d_off;
+    q.n_lists = n_chunks;
+    q.rec_tok = c.rec_tok;
+    q.rec_cnt = c.rec_cnt;
+    q.pk_off = c.pk_off;
+    q.R = R;
+    q.rows_cap = rows_cap;
+    q.seed = P.seed;
+    q.S = P.S;
+    q.B = P.B;
+    q.cls = tok.tpl_cls;  // (the loaded BertProcessing's own ids: P.pre / P.post hold the reference's doubled framing)
+    q.sep = tok.tpl_sep;
+    q.mask_length = P.mask_length;
+    q.mask_id = P.mask_id;
+    q.mp = mpol;
+    q.carry_ids = c.carry_ids;
+    q.carry_pos = c.carry_pos;
+    q.carry_len = c.carry_len;
+    q.new_ids = c.new_ids;
+    q.new_pos = c.new_pos;
+    q.new_len = c.new_len;
+    q.row_cnt = cnt + pk_cur;
+    q.new_row_cnt = cnt + (pk_cur ^ 1);
+    q.ids = o_ids.p;
+    q.am = o_am.p;
+    q.tt = o_tt0.p;
+    q.lab = o_lab.p;
+    q.pos = o_tt.p;
+    q.d_rows = pk_meta.p;
+    return q;
+}
+// the call's rows from rec_tok / rec_cnt and the chunk lists (after launch_records): packed lengths
+// with [CLS] and [SEP], their scan seeded with the carry length, the masked rows and the new carry
+// -- no host synchronisation
+void sdl_batcher::run_pack_mlm(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st) {
+    pk_off.ensure((size_t)R + 1);
+    HIP_TRY(launch_pack_lengths(pack_params(R, rows_cap), st, 2));
+    HIP_TRY(launch_exclusive_scan(rec_rows.p, pk_off.p, R, scan_tmp.p, st, pk_off.p));
+    HIP_TRY(launch_pack_mlm_rows(pack_mlm_params(R, rows_cap, n_chunks, d_off), st));
+    pk_cur ^= 1;
+    pk_ran = true;
+}
 // the flush row into row 0 of the planes (0 rows when the carry is empty); empties the carry
 void sdl_batcher::run_pack_flush(hipStream_t st) {
     const int64_t rows_cap = P.B;
@@ -91,7 +141,12 @@ void sdl_batcher::run_pack_flush(hipStream_t st) {
     o_am.ensure(plane);
     o_tt.ensure(plane);
     o_lab.ensure(plane);
-    HIP_TRY(launch_pack_flush(pack_params(0, rows_cap), st));
+    if (pack_mlm()) {
+        o_tt0.ensure(plane);
+        HIP_TRY(launch_pack_mlm_flush(pack_mlm_params(0, rows_cap, 0, nullptr), st));
+    } else {
+        HIP_TRY(launch_pack_flush(pack_params(0, rows_cap), st));
+    }
     pk_cur ^= 1;
     pk_ran = true;
     last_rows_cap = rows_cap;
@@ -172,6 +227,7 @@ int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     const int64_t ids = dt.kind == TOK_UNIGRAM ? 2 * N + 1024 * 1024 : N;
     int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
     if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
+    if (pack_mlm()) cap = (ids + 2 * R + P.S - 1) / P.S + 1;  // ... + a [CLS] and a [SEP] per record
     if (pair()) cap = R / 2;                          // a row per pair of text ranges
     return (cap + P.B - 1) / P.B * P.B;
 }
@@ -206,6 +262,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
     o_ids.ensure(plane);
     o_am.ensure(plane);
     if (plane4()) o_tt.ensure(plane);
+    if (pack_mlm()) o_tt0.ensure(plane);
     if (multi()) {
         o_f32.ensure((size_t)std::max<int64_t>(rows_cap, 1) * P.label_width);
         lab_err.ensure(1);
@@ -236,7 +293,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
     // whole call, so they run as one segment.
     SegChunks sc{};
     sc.K = 1;
-    if (!bpe && !uni && !pair() && seg_target > 1 && n_chunks >= 2 * seg_min_chunks) {
+    if (!bpe && !uni && !pair() && !pack() && seg_target > 1 && n_chunks >= 2 * seg_min_chunks) {
         sc.K = (int)std::min<int64_t>(seg_target, n_chunks / seg_min_chunks);
         sc.K = std::min(sc.K, MAX_SEGMENTS);
     }
@@ -345,7 +402,8 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
         if (!piped) mark(5);
         if (pack()) {  // rec_tok / rec_cnt exist: the stream's rows instead of row scan, row map and k_rows
             mark(6);
-            run_pack(R, rows_cap, s);
+            if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
+            else run_pack(R, rows_cap, s);
             return;
         }
         if (pair()) {  // a row per pair of text ranges instead of row scan, row map and k_rows
@@ -724,7 +782,8 @@ void fill_batch(const sdl_batcher *h, HostBatch *b, sdl_batch *out) {
     b->init_tail();
     out->input_ids = b->ids;
     out->attention_mask = b->am;
-    out->token_type_ids = b->tt_is_pos ? nullptr : b->tt;  // (position_ids: sdl_batch_position_ids)
+    // (position_ids: sdl_batch_position_ids; packed mlm: the shared zero plane, kept alive by the batch)
+    out->token_type_ids = !b->tt_is_pos ? b->tt : b->zero_tt ? b->zero_tt->data() : nullptr;
     out->labels = b->lab;
     out->labels_f32 = b->f32;
     out->owner_ = b;
@@ -793,6 +852,17 @@ int check_config(const sdl_config *cfg) {
     if (cfg->pair < SDL_PAIR_NONE || cfg->pair > SDL_PAIR_MLM_SOP)
         return fail(SDL_ERR_ARG, "pair must be 0 (one text per record), 1 (sentence pairs) or 2..4 (mlm sentence pairs); "
                                  "other values are reserved");
+    // (packed mlm rows next, so that each of their refusals names pack)
+    if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM) {
+        if (cfg->mask_policy == SDL_MASK_REFERENCE)
+            return fail(SDL_ERR_ARG, "pack = 1 under the MLM task needs mask_policy 1 or 2: the reference's rule masks "
+                                     "[CLS] / [SEP] and defines nothing for packed rows");
+        if (cfg->pair != SDL_PAIR_NONE) return fail(SDL_ERR_ARG, "pack = 1 under the MLM task needs pair = 0");
+        if (cfg->sequence_length < 3 || cfg->sequence_length > 2048)
+            return fail(SDL_ERR_ARG, "pack = 1 under the MLM task needs 3 <= sequence_length <= 2048");
+        if (cfg->rng_mode == 1)
+            return fail(SDL_ERR_UNSUPPORTED, "pack = 1 under the MLM task needs rng_mode 0: the masks are on the Philox contract");
+    }
     if (cfg->pair >= SDL_PAIR_MLM) {
         if (cfg->task != SDL_TASK_MLM)
             return fail(SDL_ERR_ARG, "pair = 2..4 (mlm sentence pairs, NSP / SOP draws) apply to the MLM task only");
@@ -838,7 +908,8 @@ int check_config(const sdl_config *cfg) {
                         "mask_policy 1 / 2 need rng_mode 0: the reference's own draws define no such policy");
     }
     if (cfg->pack != 0 && cfg->pack != 1) return fail(SDL_ERR_ARG, "pack must be 0 (off) or 1 (packed rows)");
-    if (cfg->pack == 1 && cfg->task != SDL_TASK_CLM) return fail(SDL_ERR_ARG, "pack = 1 applies to the CLM task only");
+    if (cfg->pack == 1 && cfg->task != SDL_TASK_CLM && cfg->task != SDL_TASK_MLM)
+        return fail(SDL_ERR_ARG, "pack = 1 applies to the CLM and MLM tasks only");
     if (cfg->span_policy < SDL_SPAN_REFERENCE || cfg->span_policy > SDL_SPAN_T5)
         return fail(SDL_ERR_ARG, "span_policy must be 0 (reference) or 1 (T5)");
     if (cfg->span_policy == SDL_SPAN_T5) {
@@ -1109,7 +1180,7 @@ int process_device_checked(sdl_batcher *h, const uint8_t *d_text, uint64_t text_
         std::memset(out, 0, sizeof(*out));
         out->input_ids = h->o_ids.p;
         out->attention_mask = h->o_am.p;
-        out->token_type_ids = h->with_tt() ? h->o_tt.p : nullptr;
+        out->token_type_ids = h->pack_mlm() ? h->o_tt0.p : h->with_tt() ? h->o_tt.p : nullptr;
         out->labels = h->multi() ? nullptr : h->o_lab.p;
         out->labels_f32 = h->multi() ? h->o_f32.p : nullptr;
         out->d_label_errors = h->simple() ? h->lab_err.p : h->span() ? h->span_err.p : nullptr;
@@ -1172,11 +1243,17 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             return fail(SDL_ERR_UNSUPPORTED,
                         "pair = 2..4 with a byte-level BPE or Unigram tokenizer: mlm sentence pairs need a WordPiece "
                         "tokenizer with [CLS] and [SEP] ids");
+        // (and packed mlm rows, for the same reason)
+        if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM &&
+            (h->tok.kind != TOK_WORDPIECE || h->tok.tpl_cls < 0 || h->tok.tpl_sep < 0))
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pack = 1 under the MLM task needs a WordPiece tokenizer with [CLS] and [SEP] ids: packed mlm "
+                        "rows are not built for byte-level BPE or Unigram tokenizers");
         if (cfg->mask_policy == SDL_MASK_BERT_WHOLE_WORD && h->tok.kind != TOK_WORDPIECE)
             return fail(SDL_ERR_UNSUPPORTED,
                         "mask_policy 2 (SDL_MASK_BERT_WHOLE_WORD) needs a WordPiece tokenizer: whole words are "
                         "not defined for byte-level BPE or Unigram pieces");
-        if (cfg->pack == 1 && (h->tok.kind != TOK_BYTE_BPE || h->tok.eos_id < 0))
+        if (cfg->pack == 1 && cfg->task == SDL_TASK_CLM && (h->tok.kind != TOK_BYTE_BPE || h->tok.eos_id < 0))
             return fail(SDL_ERR_UNSUPPORTED,
                         "pack = 1 needs a byte-level BPE tokenizer with an <|endoftext|> id: packed rows are "
                         "not built for WordPiece or Unigram tokenizers");
@@ -1195,8 +1272,8 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
         fill_row_params(h.get());
         if (h->pack()) {  // an empty carry in both halves
             h->pk_carry.ensure(4 * (size_t)h->P.S);
-            h->pk_meta.ensure(4);
-            HIP_TRY(hipMemsetAsync(h->pk_meta.p, 0, 4 * sizeof(uint32_t), h->stream));
+            h->pk_meta.ensure(sdl_batcher::PK_META_WORDS);
+            HIP_TRY(hipMemsetAsync(h->pk_meta.p, 0, sdl_batcher::PK_META_WORDS * sizeof(uint32_t), h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));  // (the first call may come on a caller's stream)
         }
         h->store.push_back(h->new_batch());  // GenTokenizer::new: first DataSet
@@ -1382,6 +1459,7 @@ int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out) {
         std::memset(out, 0, sizeof(*out));
         out->input_ids = h->o_ids.p;
         out->attention_mask = h->o_am.p;
+        out->token_type_ids = h->pack_mlm() ? h->o_tt0.p : nullptr;
         out->labels = h->o_lab.p;
         out->d_rows = h->pk_meta.p;
         out->rows_capacity = (uint64_t)h->last_rows_cap;
@@ -1478,6 +1556,10 @@ int sdl_multi_create(const sdl_config *cfg, const char *tokenizer_path, const ch
         return fail(SDL_ERR_UNSUPPORTED,
                     "sdl_multi_create with pair = 2..4: sentence pairs are not sharded over several handles (a next-"
                     "sentence draw is over one call's pairs)");
+    if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM)
+        return fail(SDL_ERR_UNSUPPORTED,
+                    "sdl_multi_create with pack = 1 under the MLM task: every shard would mask its rows with the same "
+                    "packed indices; give each shard's handle its own seed");
     std::unique_ptr<sdl_multi> m(new sdl_multi());
     m->next_record = cfg->first_record;
     for (uint32_t k = 0; k < n_devices; ++k) {

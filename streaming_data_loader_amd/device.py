@@ -24,7 +24,7 @@ class _CudaView:
 class DeviceResult:
     def __init__(self, handle, rows_struct, n_records, S, B=None, device=0, stream=0, pos_ptr=None, pair_ptr=None):
         self.h = handle
-        self.pos_ptr = pos_ptr  # packed clm rows: the position_ids plane (sdl_device_position_ids)
+        self.pos_ptr = pos_ptr  # packed rows: the position_ids plane (sdl_device_position_ids)
         self.pair_ptr = pair_ptr  # mlm sentence pairs: the pair labels (sdl_device_pair_labels)
         self.r = rows_struct
         self.n_records = n_records
@@ -82,7 +82,7 @@ class DeviceResult:
         return (get(self.r.input_ids, S), get(self.r.attention_mask, S), get(self.r.token_type_ids, S), lab)
 
     def position_ids(self, n_rows=None):
-        """Packed clm rows (DeviceBatcher(pack=1)): the position_ids plane as numpy [n, S]; None otherwise."""
+        """Packed rows (DeviceBatcher(pack=1), clm or mlm): the position_ids plane as numpy [n, S]; None otherwise."""
         if not self.pos_ptr:
             return None
         n = self.rows() if n_rows is None else n_rows
@@ -115,7 +115,7 @@ class DeviceResult:
         for key, ptr, w, ts in (("input_ids", self.r.input_ids, S, "<i4"),
                                 ("attention_mask", self.r.attention_mask, S, "<i4"),
                                 ("token_type_ids", self.r.token_type_ids, S, "<i4"),
-                                ("position_ids", self.pos_ptr, S, "<i4"),  # packed clm rows only
+                                ("position_ids", self.pos_ptr, S, "<i4"),  # packed rows only
                                 ("labels", self.r.labels_f32 or self.r.labels, LW, "<f4" if self.r.labels_f32 else "<i4")):
             if ptr and n > 0:
                 out[key] = torch.as_tensor(_CudaView(ptr, (n, w), ts, self.stream), device=dev)
@@ -214,7 +214,7 @@ class DeviceBatcher:
                             stream, native.load().sdl_device_position_ids(self._h))
 
     def flush_device(self, stream=0):
-        """Packed clm rows (pack=1): the carry as one last row (sdl_pack_flush_device) -- a result
+        """Packed rows (pack=1): the carry as one last row (sdl_pack_flush_device; masked under mlm) -- a result
         of 0 or 1 rows in row 0 of the planes; the carry is empty afterwards."""
         out = native.DeviceRows()
         native.check(native.load().sdl_pack_flush_device(self._h, ctypes.c_void_p(stream or None), ctypes.byref(out)))

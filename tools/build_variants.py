@@ -27,6 +27,9 @@ DIAG_MACROS = {
     # span policy 1: 1 = keys without Philox, 2 = also no selection and no compaction (rows not
     # the contract's): where k_rows_span_t5's time goes (build.build_span_ablations, var/span_abl{1,2})
     "SDL_SPAN_T5_ABLATE": "k_rows_span_t5 without its keys / its selections",
+    # packed mlm rows: 1 = no pick and no draws, 2 = also no list reads (rows not the contract's):
+    # where k_pack_mlm_rows' time goes (build.build_pack_mlm_ablations, var/pack_mlm_abl{1,2})
+    "SDL_PACK_MLM_ABLATE": "k_pack_mlm_rows without its pick / its list reads",
 }
 
 
