@@ -177,10 +177,7 @@ __device__ __forceinline__ void pack_mlm_row(const PackMlmParams &q, uint32_t g,
             if (256 * m + 4 * lane + w < l && !ex) cand |= 1u << (4 * m + w);
         }
     const int ncand = (int)wv.sum((uint32_t)__popc(cand));
-    int kb = (int)(((int64_t)l * mp.per_mille + 500) / 1000);
-    kb = kb < 1 ? 1 : kb;
-    kb = kb < q.mask_length ? kb : q.mask_length;
-    if (ncand == 0) kb = 0;
+    int kb = policy_budget(l, ncand, mp.per_mille, q.mask_length);
 #if SDL_PACK_MLM_ABLATE >= 1  // (diagnostic: no keys, no pick, no draws; the rows are not the contract's)
     kb = 0;
 #endif
@@ -298,7 +295,7 @@ __device__ __forceinline__ void pack_mlm_row(const PackMlmParams &q, uint32_t g,
             bool any_rand = false;
 #pragma unroll
             for (int w = 0; w < 4; ++w)
-                any_rand = any_rand || ((s4 >> w) & 1u && u[w] >= 0xCCCCCCCDu && u[w] < 0xE6666667u);
+                any_rand = any_rand || ((s4 >> w) & 1u && u[w] >= POLICY_MASK_BELOW && u[w] < POLICY_RANDOM_BELOW);
             uint32_t rr[4] = {0u, 0u, 0u, 0u};
             if (any_rand) {
                 const uint4 r4 = philox4x32_10(make_uint4((uint32_t)(64 * m + lane), 0x30000000u, (uint32_t)rec,
@@ -313,8 +310,8 @@ __device__ __forceinline__ void pack_mlm_row(const PackMlmParams &q, uint32_t g,
             for (int w = 0; w < 4; ++w)
                 if ((s4 >> w) & 1u) {
                     lab[w] = v[w];
-                    if (u[w] < 0xCCCCCCCDu) v[w] = q.mask_id;
-                    else if (u[w] < 0xE6666667u) v[w] = (int32_t)__umulhi(rr[w], mp.vocab_size);
+                    if (u[w] < POLICY_MASK_BELOW) v[w] = q.mask_id;
+                    else if (u[w] < POLICY_RANDOM_BELOW) v[w] = (int32_t)__umulhi(rr[w], mp.vocab_size);
                 }
         }
         store4(ids_o, j0, S, vec, v[0], v[1], v[2], v[3]);

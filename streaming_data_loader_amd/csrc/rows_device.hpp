@@ -1,14 +1,15 @@
 // Device code shared by the rows kernels (pipeline.hip) and the fused tiny-push tail of the
 // WordPiece chunk kernel (tokenize_wordpiece.hip): chunk-list compaction, per-record framing,
-// the Philox mask contract and one row's planes.  A row's ids come from the dense array the
-// compaction makes, or (WordPiece, large calls: row_one<.., LISTS>) straight from the packed u16
-// chunk lists the tokenizer wrote, indexed as list_index.hpp says.
+// one row's planes under the reference's masking rule or the BERT policies (the Philox contract,
+// the select and the policies' shared pieces: mlm_policy_device.hpp).  A row's ids come from the
+// dense array the compaction makes, or (WordPiece, large calls: row_one<.., LISTS>) straight from
+// the packed u16 chunk lists the tokenizer wrote, indexed as list_index.hpp says.
 #pragma once
 #include "common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
 #include "list_index.hpp"
-#include "mlm_pick.hpp"
+#include "mlm_policy_device.hpp"
 
 namespace sdl {
 
@@ -176,21 +177,7 @@ __device__ __forceinline__ uint32_t record_one(const RowParams &P, const uint64_
     return rows;
 }
 
-// ---------------------------------------------------------------------------
-// RNG contract: Philox4x32-10 (Salmon et al., SC'11), as oracle/sdl_oracle.c.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
+// key of position pos of a record's chunk (the Philox contract, mlm_policy_device.hpp)
 __device__ __forceinline__ uint32_t mlm_key(uint64_t seed, uint64_t rec, uint32_t chunk, uint32_t pos) {
     const uint4 c = philox4x32_10(make_uint4(pos >> 2, chunk, (uint32_t)rec, (uint32_t)(rec >> 32)), (uint32_t)seed,
                                   (uint32_t)(seed >> 32));
@@ -203,114 +190,9 @@ __device__ __forceinline__ int32_t frame_id(const int32_t (&a)[MAX_FRAME], int k
     return k == 0 ? a[0] : k == 1 ? a[1] : k == 2 ? a[2] : a[3];
 }
 
-// Row layout of k_rows: lane L owns positions 256*m + 4*L + w (w = 0..3), so
-// one Philox block (4 words) is exactly one lane's keys for round m and every
-// plane store is one 16-byte write per lane.
-//
-// Marks the k smallest (key, position) pairs of a row held as key[m][w]: a
-// radix select of the k-th smallest key with wave ballots, then a
-// position-ordered tie-break among keys equal to it.  The descent stops as soon
-// as exactly k keys lie below the candidate (after ~log2(S) + 2 of the 32
-// steps for distinct keys), which selects the same set.
-template <int MR>
-__device__ __forceinline__ void select_k_smallest(const uint32_t (&key)[MR][4], int k, bool (&sel)[MR][4]) {
-    if (k <= 0) {
-#pragma unroll
-        for (int m = 0; m < MR; ++m)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) sel[m][w] = false;
-        return;
-    }
-    uint32_t prefix = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t cand = prefix | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int m = 0; m < MR; ++m)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) c += __popcll(__ballot(key[m][w] < cand));
-        if (c == k) {  // exactly the k smallest keys lie below cand: no tie to break
-#pragma unroll
-            for (int m = 0; m < MR; ++m)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) sel[m][w] = key[m][w] < cand;
-            return;
-        }
-        if (c < k) prefix = cand;
-    }
-    int c_lt = 0;
-#pragma unroll
-    for (int m = 0; m < MR; ++m)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) c_lt += __popcll(__ballot(key[m][w] < prefix));
-    const int need = k - c_lt;
-    const uint64_t lt_mask = (1ull << lane_id()) - 1ull;
-    int before = 0;  // equal keys in earlier rounds
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-        uint64_t eq[4];
-        int lower = 0;  // equal keys of this round in lower lanes
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            eq[w] = __ballot(key[m][w] == prefix);
-            lower += __popcll(eq[w] & lt_mask);
-        }
-        int own = 0;  // equal keys of this lane at lower w
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const bool e = key[m][w] == prefix;
-            sel[m][w] = key[m][w] < prefix || (e && before + lower + own < need);
-            own += e ? 1 : 0;
-        }
-#pragma unroll
-        for (int w = 0; w < 4; ++w) before += __popcll(eq[w]);
-    }
-}
-
-// The same selection, usually in far fewer steps: the Philox keys are uniform,
-// so an interpolation search over the key range (the next threshold guessed
-// from the counts at the bracket's ends) lands on a threshold with exactly k
-// keys below it in ~3-4 counts instead of the radix descent's ~log2(S) + 2.
-// Any threshold with exactly k keys below it marks the same k-smallest set; a
-// tie at the k-th key (no such threshold) or a slow bracket falls back to the
-// radix select.
-constexpr int ROWS_INTERP_STEPS = 8;
-template <int MR>
-__device__ __forceinline__ void select_k_smallest_interp(const uint32_t (&key)[MR][4], int k, int nvalid,
-                                                         bool (&sel)[MR][4]) {
-    if (k > 0 && k < nvalid) {
-        uint32_t lo = 0, hi = 0xFFFFFFFFu;  // count(key < lo) = c_lo < k < c_hi ~ count(key < hi)
-        int c_lo = 0, c_hi = nvalid;
-#pragma unroll 1
-        for (int it = 0; it < ROWS_INTERP_STEPS && hi - lo > 1u; ++it) {
-            const float f = ((float)(k - c_lo) + 0.5f) / (float)(c_hi - c_lo);
-            uint32_t cand = lo + (uint32_t)((float)(hi - lo) * f);
-            cand = cand <= lo ? lo + 1u : cand >= hi ? hi - 1u : cand;
-            cand = __builtin_amdgcn_readfirstlane(cand);
-            int c = 0;
-#pragma unroll
-            for (int m = 0; m < MR; ++m)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) c += __popcll(__ballot(key[m][w] < cand));
-            if (c == k) {
-#pragma unroll
-                for (int m = 0; m < MR; ++m)
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) sel[m][w] = key[m][w] < cand;
-                return;
-            }
-            if (c < k) {
-                lo = cand;
-                c_lo = c;
-            } else {
-                hi = cand;
-                c_hi = c;
-            }
-        }
-    }
-    select_k_smallest<MR>(key, k, sel);
-}
-
+// Row layout of k_rows: lane L owns positions 256*m + 4*L + w (w = 0..3), so one Philox block
+// (4 words) is exactly one lane's keys for round m (mlm_policy_device.hpp) and every plane store is
+// one 16-byte write per lane.
 __device__ __forceinline__ void store4(int32_t *p, int j0, int S, bool vec, int32_t a, int32_t b, int32_t c,
                                        int32_t d) {
     if (vec) {  // the planes stream out: non-temporal, they are not re-read by this pass
@@ -844,24 +726,6 @@ __device__ __forceinline__ void row_fast_one(RowArgs a, uint32_t g, uint32_t G, 
     row_fast_store<MR, TASK>(a, g, lane, v, am, lab);
 }
 
-// ---------------------------------------------------------------------------
-// The BERT masking policies (sdl_config.mask_policy 1 / 2; DESIGN.md §3 "Masking policies").
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t max_u32(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t min_u32r(uint32_t a, uint32_t b) { return a < b ? a : b; }
-// the wave, as mlm_pick.hpp asks for it: sums and minima over all lanes, uniform
-struct PickWave {
-    uint32_t l;
-    __device__ __forceinline__ uint32_t sum(uint32_t x) const {
-        return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_sum(x), 63);
-    }
-    __device__ __forceinline__ uint32_t min(uint32_t x) const {
-        DPP_SCAN_ID(x, min_u32r, 0xFFFFFFFFu);
-        return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-    }
-    __device__ __forceinline__ uint32_t lane() const { return l; }
-};
-
 // One MLM row g under policy 1 (WHOLE = false: every candidate a unit) or 2 (whole words), a wave:
 // row_one's geometry, framing, attention and stores; the pick and the 80/10/10 replacement are
 // the contract's.  A lane's masks are a bit per element, bit 4 m + w = position 256 m + 4 lane + w.
@@ -932,10 +796,7 @@ __device__ __forceinline__ void row_policy_one(const RowParams &P, const MaskPol
             if (256 * m + 4 * lane + w < l && !ex) cand |= 1u << (4 * m + w);
         }
     const int ncand = (int)wv.sum((uint32_t)__popc(cand));
-    int kb = (int)(((int64_t)l * mp.per_mille + 500) / 1000);
-    kb = kb < 1 ? 1 : kb;
-    kb = kb < P.mask_length ? kb : P.mask_length;
-    if (ncand == 0) kb = 0;
+    const int kb = policy_budget(l, ncand, mp.per_mille, P.mask_length);
 
     uint32_t sel = 0;  // the picked positions
     if (kb > 0) {  // (wave-uniform)
@@ -1049,7 +910,7 @@ __device__ __forceinline__ void row_policy_one(const RowParams &P, const MaskPol
             bool any_rand = false;
 #pragma unroll
             for (int w = 0; w < 4; ++w)
-                any_rand = any_rand || ((s4 >> w) & 1u && u[w] >= 0xCCCCCCCDu && u[w] < 0xE6666667u);
+                any_rand = any_rand || ((s4 >> w) & 1u && u[w] >= POLICY_MASK_BELOW && u[w] < POLICY_RANDOM_BELOW);
             uint32_t rr[4] = {0u, 0u, 0u, 0u};
             if (any_rand) {
                 const uint4 r4 = philox4x32_10(make_uint4((uint32_t)(64 * m + lane), ck | 0x30000000u, (uint32_t)rec,
@@ -1064,8 +925,8 @@ __device__ __forceinline__ void row_policy_one(const RowParams &P, const MaskPol
             for (int w = 0; w < 4; ++w)
                 if ((s4 >> w) & 1u) {
                     lab[w] = v[w];
-                    if (u[w] < 0xCCCCCCCDu) v[w] = P.mask_id;
-                    else if (u[w] < 0xE6666667u) v[w] = (int32_t)__umulhi(rr[w], mp.vocab_size);
+                    if (u[w] < POLICY_MASK_BELOW) v[w] = P.mask_id;
+                    else if (u[w] < POLICY_RANDOM_BELOW) v[w] = (int32_t)__umulhi(rr[w], mp.vocab_size);
                 }
         }
         store4(ids_o, j0, S, vec, v[0], v[1], v[2], v[3]);
