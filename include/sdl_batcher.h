@@ -32,9 +32,9 @@
 extern "C" {
 #endif
 
-/* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device, the three sentence-pair calls and the
- * two pair-label accessors were added without changing any existing call or struct (an additive
- * change keeps the version). */
+/* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device, the three sentence-pair calls, the
+ * two pair-label accessors and sdl_pack_span_length were added without changing any existing call
+ * or struct (an additive change keeps the version). */
 #define SDL_ABI_VERSION 9
 
 enum {
@@ -92,7 +92,9 @@ struct sdl_config {
                                 rows); 1 = documents concatenated with the end-of-text id and the stream
                                 cut into full rows ("Packed rows" below).  Carved out of reserved[4].
                                 MLM, WordPiece, mask_policy 1 / 2: 1 = [CLS] ids [SEP] documents
-                                concatenated, cut into full rows and masked ("Packed mlm rows" there) */
+                                concatenated, cut into full rows and masked ("Packed mlm rows" there).
+                                Span, Unigram, span_policy 1: 1 = ids </s> documents concatenated, cut into
+                                chunks that fill a row once corrupted ("Packed span rows" there) */
     union {                  /* the last three words under two views: a zeroed config is the reference's */
         int32_t reserved[3];
         struct {
@@ -197,7 +199,28 @@ typedef struct sdl_batcher sdl_batcher;
  * not WordPiece (SDL_ERR_UNSUPPORTED); sdl_json_to_frames and sdl_multi_create return
  * SDL_ERR_UNSUPPORTED (shards would reuse one index range: give each handle its own seed);
  * sdl_pickle_frames_device frames the four mlm keys over the packed planes, no position_ids key.
- * sdl_batch.token_type_ids is one read-only zero plane shared by the handle's batches. */
+ * sdl_batch.token_type_ids is one read-only zero plane shared by the handle's batches.
+ *
+ * Packed span rows (pack = 1 with task span, the Unigram tokenizer, span_policy 1, rng_mode 0):
+ * T5's pre-training chunks (t5.data.preprocessors.span_corruption, HF run_t5_mlm_flax.py).  The
+ * stream is the clm one with eos = the tokenizer's </s> (record r kept when n_r >= 1 and
+ * n_r + 1 >= min_ids), but it is cut into chunks of N > S ids: with t(n), m(n) policy 1's counts
+ * and u = n - t, N is the last n in 1..65535 before the first n with u(n) + m(n) > S
+ * (sdl_pack_span_length), so a corrupted chunk fills the S input columns (S - 1 where the counts
+ * step by two).  A stream of L ids gives G = L / N rows, stream[G N, L) is the carry (ids only),
+ * and row g is the "Span policies" row of chunk stream[g N, (g + 1) N) as chunk 0 of record q, the
+ * number of packed rows the handle emitted before it, flush rows included: the same counters,
+ * domains, cuts, sentinels and planes (attention_mask 1 below u + m, S/4 labels with -100 behind
+ * the t + m + 1 entries), so the rows of any split of a record list into calls are the rows of one
+ * call and first_record is unused.  No position_ids plane (T5 takes none) and no token_type_ids;
+ * no EOS beyond the documents' own.  A flush turns a carry of c > 0 ids into one more row by the
+ * same rule with n = c.  Rows from *d_rows to the next multiple of B hold T5Data::new's values
+ * (0, 1, -100); d_label_errors is always 0; d_record_rows[r] = n_r + 1 or 0; rows_capacity =
+ * (ids + R + N - 1) / N + 1 rounded up to B.  sdl_batcher_create refuses, naming pack:
+ * span_policy 0 and a chunk with t(N) + m(N) + 1 > S/4, m(N) + 1 > 100 or N > 3584 (SDL_ERR_ARG;
+ * this replaces policy 1's full-row rule), a tokenizer that is not Unigram (SDL_ERR_UNSUPPORTED);
+ * sdl_multi_create and sdl_json_to_frames return SDL_ERR_UNSUPPORTED; sdl_pickle_frames_device
+ * frames the three span keys over the packed planes.  The host path is the clm one above. */
 
 /* ---- Sentence pairs (sdl_config.pair = 1; tasks single-class and multi-label, WordPiece) ----
  * No counterpart in the reference (SimpleData.alt_text is tokenized and dropped, dataset.rs:47):
@@ -353,6 +376,10 @@ int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out);
 /* pack = 1: the position_ids plane, device [rows_capacity, S], of the handle's last
  * sdl_process_device / sdl_pack_flush_device call; NULL when pack = 0 or before the first call. */
 const int32_t *sdl_device_position_ids(sdl_batcher *h);
+/* Packed span rows: the chunk length N of a config with task span, pack = 1 and span_policy 1
+ * ("Packed span rows" above), or a negative SDL_ERR_* with sdl_last_error set when
+ * sdl_batcher_create would refuse the config's words.  Host only: needs no GPU. */
+int sdl_pack_span_length(const sdl_config *cfg);
 
 /* sdl_process_device for the multi-label task with Label::Multi indices per
  * record: record r's indices are d_labels[d_label_offsets[r] .. d_label_offsets[r+1])

@@ -63,6 +63,9 @@ class Span:
     # of mean length avg_span_size (T5: 3.0), avg_span_gap ignored
     policy: int = 0
     noise_per_mille: int = 0
+    # sdl_config.pack (DESIGN.md §3 "Packed span rows", policy 1 only): documents concatenated with
+    # </s>, the stream cut into chunks that fill a row once corrupted; no position_ids plane
+    pack: bool = False
 
 
 @dataclass
@@ -219,7 +222,7 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
         c.mask_length, c.mask_id = dataset_config.mask_length, dataset_config.mask
         c.mask_policy, c.mask_per_mille = dataset_config.mask_policy, dataset_config.mask_per_mille
         c.pair = int(dataset_config.pair)
-    if isinstance(dataset_config, (Gpt, Mask)):
+    if isinstance(dataset_config, (Gpt, Mask, Span)):
         c.pack = 1 if dataset_config.pack else 0
     if isinstance(dataset_config, Span):
         c.avg_span_gap, c.avg_span_size = dataset_config.avg_span_gap, dataset_config.avg_span_size

@@ -21,7 +21,7 @@ BUILD = os.path.join(REPO, "build", "sdl")
 LIB = os.path.join(PKG, "libsdl_batcher.so")
 ARCH = os.environ.get("SDL_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pack_mlm.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
+SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pack_mlm.hip", "pack_span.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
            "assets.cpp", "sdl_batcher.cpp", "provider_json.cpp", "provider_gzip.cpp", "provider_zstd.cpp", "transport.cpp"]
 HEADERS = ["common.hpp", "device_util.hpp", "kernels.hpp", "tok_device.hpp", "assets.hpp", "json.hpp", "unigram.hpp", "handle.hpp",
            "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "mlm_policy_device.hpp", "span_noise.hpp", "pair_draw.hpp", "pack_queue.hpp", "pack_search.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
@@ -29,7 +29,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
          "-I", os.path.join(REPO, "include"), "-I", CSRC]
 # per-source flags on top of FLAGS: newer kernels are compiled without packed fp32 instructions
 # (the older sources keep the flags, and so the machine code, they had)
-EXTRA_FLAGS = {"pack_mlm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"pack_mlm.hip": NO_PACKED_FP32, "pack_span.hip": NO_PACKED_FP32}
 
 
 def _hipcc():
@@ -228,6 +229,15 @@ def build_pack_mlm_ablations(levels=(1, 2)):
     mlm rows": where the packed rows stage spends its time)."""
     return [build(defines=(f"SDL_PACK_MLM_ABLATE={n}",), lib=os.path.join(REPO, "var", f"pack_mlm_abl{n}", "libsdl_batcher.so"),
                   build_dir=os.path.join(REPO, "build", f"pack_mlm_abl{n}")) for n in levels]
+
+
+def build_pack_span_ablations(levels=(1, 2)):
+    """Diagnostic builds of k_pack_span_rows (SDL_PACK_SPAN_ABLATE: 1 no Philox, 2 no keys and no selection: the
+    staging, the plan and the stores are left; their rows are not the contract's) ->
+    var/pack_span_abl{n}/libsdl_batcher.so, for SDL_LIB=... tools/pack_span_bench.py (DESIGN.md §4 "Packed
+    span rows": where the packed rows stage spends its time)."""
+    return [build(defines=(f"SDL_PACK_SPAN_ABLATE={n}",), lib=os.path.join(REPO, "var", f"pack_span_abl{n}", "libsdl_batcher.so"),
+                  build_dir=os.path.join(REPO, "build", f"pack_span_abl{n}")) for n in levels]
 
 
 if __name__ == "__main__":

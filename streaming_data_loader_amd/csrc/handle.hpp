@@ -472,7 +472,10 @@ struct sdl_batcher {
     // types -- all 0 in a packed row -- are a plane of their own on the device (o_tt0) and one
     // shared zero plane for the host batches (zero_tt): sdl_batch and sdl_device_rows keep their sizes
     bool pack_mlm() const { return pack() && P.task == SDL_TASK_MLM; }
-    bool plane4() const { return with_tt() || pack(); }
+    // ... and under the span task (pack_span.hip): chunks of pack_span_N > S stream ids corrupted into
+    // S-wide rows; ids only -- no position_ids plane, so the batches have no fourth plane
+    bool pack_span() const { return pack() && P.task == SDL_TASK_SPAN; }
+    bool plane4() const { return with_tt() || (pack() && !pack_span()); }
     // sdl_config.pair != 0: a call's 2 n text ranges are n examples of two texts, one row each
     // (pair = 1: pair.hip, the label tasks; pair 2..4: pair_mlm.hip, mlm with a drawn pair label)
     bool pair() const { return cfg.pair != 0; }
@@ -482,7 +485,7 @@ struct sdl_batcher {
     HostBatch *new_batch() {
         if (!pool) pool = std::make_shared<BatchPool>(HostBatch::block_bytes(P.B, P.S, P.label_width, plane4()));
         HostBatch *b = new HostBatch(pool, P.B, P.S, P.label_width, plane4(), multi());
-        b->tt_is_pos = pack();
+        b->tt_is_pos = pack() && !pack_span();
         if (pack_mlm()) {
             if (!zero_tt) zero_tt = std::make_shared<std::vector<int32_t>>((size_t)P.B * (size_t)P.S, 0);
             b->zero_tt = zero_tt;
@@ -492,7 +495,7 @@ struct sdl_batcher {
     }
 
     // pack = 1: the carry between calls, double buffered (ids and position_ids, S each per half),
-    // and pk_meta = {rows of the last call, length of half 0, length of half 1, -, and (mlm) the
+    // and pk_meta = {rows of the last call, length of half 0, length of half 1, -, and (mlm, span) the
     // packed rows emitted so far as two 64-bit counters, half 0 and half 1}; the host only
     // knows which half is current -- it flips per call, the lengths and counters stay on the device
     static constexpr size_t PK_META_WORDS = 8;
@@ -500,6 +503,10 @@ struct sdl_batcher {
     DevBuf<int32_t> o_tt0;                          // packed mlm: the device rows' token_type_ids
     PackMlmParams pack_mlm_params(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off);
     void run_pack_mlm(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st);
+    // packed span: the chunk length (sdl_pack_span_length); the carry halves hold that many ids each
+    int pack_span_N = 0;
+    PackSpanParams pack_span_params(int64_t R, int64_t rows_cap);
+    void run_pack_span(int64_t R, int64_t rows_cap, hipStream_t st);
     DevBuf<int32_t> pk_carry;
     DevBuf<uint32_t> pk_meta, pk_off;
     int pk_cur = 0;

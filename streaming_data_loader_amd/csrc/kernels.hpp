@@ -465,6 +465,36 @@ hipError_t launch_pack_mlm_rows(const PackMlmParams &q, hipStream_t st);
 // the carry as one last masked row (0 rows when it is empty), rows < B of the planes; the new carry is empty
 hipError_t launch_pack_mlm_flush(const PackMlmParams &q, hipStream_t st);
 
+// pack_span.hip: T5 pre-training chunks of N > S ids cut from the stream of ids </s> documents and
+// corrupted by T5's span policy into S-wide rows (sdl_config.pack = 1 under the span task with
+// span_policy 1, DESIGN.md §3 "Packed span rows"), after launch_records, launch_pack_lengths(.., 1)
+// and the seeded scan into pk_off.  A struct of its own again: k_rows_span_t5 and k_pack_gather
+// compile to what they were.
+constexpr int PACK_SPAN_MAX_N = 3584;  // the chunk length the kernel's LDS layout holds (two waves a block)
+struct PackSpanParams {
+    const uint32_t *tok, *rec_tok, *rec_cnt;  // the dense ids and each record's first id / id count
+    const uint32_t *pk_off;                   // [R + 1]: where record r starts in the call's stream; [R] = its length
+    int64_t R, rows_cap;                      // rows_cap * N < 2^32
+    uint64_t seed;                            // the Philox key; a row's cuts are those of chunk 0 of record row_cnt + g
+    int32_t S, B, N, LW;                      // N: source ids a row (S <= N <= PACK_SPAN_MAX_N); LW = S / 4 labels
+    int32_t eos, pad;                         // the Unigram tokenizer's </s>
+    const uint32_t *counts;                   // [N + 1]: t | m << 16 for a chunk of n ids (span_noise_table)
+    const int32_t *extra_ids;                 // [100]: <extra_id_0..99>
+    const int32_t *carry_ids;                 // the carry the last call left (< N ids)
+    const uint32_t *carry_len;
+    int32_t *new_ids;                         // the other half of the double buffer: this call's carry
+    uint32_t *new_len;
+    const uint64_t *row_cnt;                  // packed rows the handle emitted before this call ...
+    uint64_t *new_row_cnt;                    // ... and after it (the other half, like the carry length)
+    int32_t *ids, *am, *lab;                  // planes [rows_cap, S], [rows_cap, S], [rows_cap, LW]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// the three planes (a wave per chunk: staged in LDS, cut and written), then the new carry, its
+// length, the row counter and d_rows
+hipError_t launch_pack_span_rows(const PackSpanParams &q, hipStream_t st);
+// the carry as one last corrupted row (0 rows when it is empty), rows < B of the planes; the new carry is empty
+hipError_t launch_pack_span_flush(const PackSpanParams &q, hipStream_t st);
+
 // pair.hip: one [CLS] A [SEP] B [SEP] row per example of two texts (sdl_config.pair = 1, DESIGN.md §3
 // "Sentence pairs"), after launch_records over the 2 * n_pairs text ranges.  A struct of its own, not
 // fields of RowParams (see MaskPolicy): the unpaired kernels compile to what they were.

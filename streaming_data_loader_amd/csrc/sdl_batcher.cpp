@@ -133,12 +133,71 @@ void sdl_batcher::run_pack_mlm(int64_t R, int64_t rows_cap, int64_t n_chunks, co
     pk_cur ^= 1;
     pk_ran = true;
 }
+// packed span: carry halves of NP ids (no position_ids), the row counter beside the carry lengths as
+// packed mlm keeps it, the dense Unigram ids, three planes with S / 4 labels a row
+PackSpanParams sdl_batcher::pack_span_params(int64_t R, int64_t rows_cap) {
+    const size_t NP = ((size_t)pack_span_N + 3) & ~(size_t)3;
+    uint64_t *cnt = reinterpret_cast<uint64_t *>(pk_meta.p + 4);
+    PackSpanParams q{};
+    q.tok = tok_ids.p;
+    q.rec_tok = rec_tok.p;
+    q.rec_cnt = rec_cnt.p;
+    q.pk_off = pk_off.p;
+    q.R = R;
+    q.rows_cap = rows_cap;
+    q.seed = P.seed;
+    q.S = P.S;
+    q.B = P.B;
+    q.N = pack_span_N;
+    q.LW = P.label_width;
+    q.eos = tok.eos_id;
+    q.counts = snoise.counts;
+    q.extra_ids = P.extra_ids;
+    q.carry_ids = pk_carry.p + (size_t)pk_cur * NP;
+    q.carry_len = pk_meta.p + 1 + pk_cur;
+    q.new_ids = pk_carry.p + (size_t)(pk_cur ^ 1) * NP;
+    q.new_len = pk_meta.p + 1 + (pk_cur ^ 1);
+    q.row_cnt = cnt + pk_cur;
+    q.new_row_cnt = cnt + (pk_cur ^ 1);
+    q.ids = o_ids.p;
+    q.am = o_am.p;
+    q.lab = o_lab.p;
+    q.d_rows = pk_meta.p;
+    return q;
+}
+// the call's rows from rec_tok / rec_cnt and the dense ids (after launch_records): packed lengths with
+// </s>, their scan seeded with the carry length, the corrupted chunks and the new carry -- no host
+// synchronisation
+void sdl_batcher::run_pack_span(int64_t R, int64_t rows_cap, hipStream_t st) {
+    pk_off.ensure((size_t)R + 1);
+    PackParams l{};  // (k_pack_lengths reads rec_cnt, rec_len, pk_off, R, min_ids and carry_len only)
+    l.rec_cnt = rec_cnt.p;
+    l.rec_len = rec_rows.p;
+    l.pk_off = pk_off.p;
+    l.R = R;
+    l.min_ids = P.min_ids;
+    l.carry_len = pk_meta.p + 1 + pk_cur;
+    HIP_TRY(launch_pack_lengths(l, st, 1));
+    HIP_TRY(launch_exclusive_scan(rec_rows.p, pk_off.p, R, scan_tmp.p, st, pk_off.p));
+    HIP_TRY(launch_pack_span_rows(pack_span_params(R, rows_cap), st));
+    pk_cur ^= 1;
+    pk_ran = true;
+}
 // the flush row into row 0 of the planes (0 rows when the carry is empty); empties the carry
 void sdl_batcher::run_pack_flush(hipStream_t st) {
     const int64_t rows_cap = P.B;
     const size_t plane = (size_t)rows_cap * P.S;
     o_ids.ensure(plane);
     o_am.ensure(plane);
+    if (pack_span()) {
+        o_lab.ensure((size_t)rows_cap * P.label_width);
+        HIP_TRY(launch_pack_span_flush(pack_span_params(0, rows_cap), st));
+        pk_cur ^= 1;
+        pk_ran = true;
+        last_rows_cap = rows_cap;
+        last_R = 0;
+        return;
+    }
     o_tt.ensure(plane);
     o_lab.ensure(plane);
     if (pack_mlm()) {
@@ -228,6 +287,7 @@ int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
     if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
     if (pack_mlm()) cap = (ids + 2 * R + P.S - 1) / P.S + 1;  // ... + a [CLS] and a [SEP] per record
+    if (pack_span()) cap = (ids + R + pack_span_N - 1) / pack_span_N + 1;  // chunks of N ids: carry (< N) + ids + a </s> per record
     if (pair()) cap = R / 2;                          // a row per pair of text ranges
     return (cap + P.B - 1) / P.B * P.B;
 }
@@ -237,7 +297,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
     const int64_t n_chunks = (N + CHUNK - 1) / CHUNK;
     const int64_t rows_cap = rows_capacity(N, R);
     // (pack.hip indexes the planes and the stream with 32 bits)
-    if (pack() && rows_cap * P.S > ((int64_t)1 << 32) - 4096)
+    if (pack() && rows_cap * (pack_span() ? pack_span_N : P.S) > ((int64_t)1 << 32) - 4096)
         throw CapacityError("pack: the call's rows exceed 2^32 positions");
     if (pair() && rows_cap * P.S > ((int64_t)1 << 32) - 4096)  // (pair.hip: a flat 32-bit work index)
         throw CapacityError("pair: the call's rows exceed 2^32 positions");
@@ -403,6 +463,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
         if (pack()) {  // rec_tok / rec_cnt exist: the stream's rows instead of row scan, row map and k_rows
             mark(6);
             if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
+            else if (pack_span()) run_pack_span(R, rows_cap, s);
             else run_pack(R, rows_cap, s);
             return;
         }
@@ -571,8 +632,8 @@ void sdl_batcher::queue_packed_rows() {
         nmax = std::max(nmax, q.n);
     }
     HIP_TRY(hipMemcpyAsync(seg_dev.p, seg_pin.p, sizeof(RowSeg) * plan.segs.size(), hipMemcpyHostToDevice, stream));
-    HIP_TRY(launch_rows_to_host(seg_dev.p, (int)plan.segs.size(), nmax, o_ids.p, o_am.p, o_tt.p, o_lab.p, P.S,
-                                P.label_width, stream));
+    HIP_TRY(launch_rows_to_host(seg_dev.p, (int)plan.segs.size(), nmax, o_ids.p, o_am.p,
+                                pack_span() ? nullptr : o_tt.p, o_lab.p, P.S, P.label_width, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (uint32_t k = 0; k < plan.completed; ++k) {
         bs[k]->rows = P.B;
@@ -843,6 +904,33 @@ std::string default_data_dir() {
     return "data";
 }
 
+// Packed span rows: the chunk length N -- the last n in 1..65535 before the first n whose corrupted
+// chunk, u(n) kept ids and m(n) sentinels, no longer fits the S input columns (u + m never
+// decreases with n) -- and the refusals of a chunk that needs more labels or sentinels than a row
+// has or more LDS than k_pack_span_rows' layout.  The caller has checked the policy's own words.
+int pack_span_length(const sdl_config *cfg, int *out) {
+    const int S = cfg->sequence_length, LW = S / 4;
+    int N = 0, t = 0, m = 0;
+    for (int n = 1; n <= 65535; ++n) {
+        span_noise_counts(n, cfg->span_noise_per_mille, cfg->avg_span_size, &t, &m);
+        if (n - t + m > S) break;
+        N = n;
+    }
+    span_noise_counts(N, cfg->span_noise_per_mille, cfg->avg_span_size, &t, &m);
+    const std::string what = "pack = 1 under the span task: a chunk of " + std::to_string(N) + " ids fills a row of " +
+                             std::to_string(S) + " and has " + std::to_string(t) + " noise ids in " +
+                             std::to_string(m) + " spans; ";
+    if (t + m + 1 > LW || m + 1 > SPAN_MAX_SENTINELS)
+        return fail(SDL_ERR_ARG, what + "it needs " + std::to_string(t + m + 1) + " labels and " + std::to_string(m + 1) +
+                                     " sentinels, the row holds " + std::to_string(LW) + " labels (S/4) and the vocabulary " +
+                                     std::to_string(SPAN_MAX_SENTINELS) +
+                                     " sentinels: lower span_noise_per_mille or raise avg_span_size");
+    if (N > PACK_SPAN_MAX_N)
+        return fail(SDL_ERR_ARG, what + "the rows kernel holds chunks of at most " + std::to_string(PACK_SPAN_MAX_N) + " ids");
+    if (out) *out = N;
+    return SDL_OK;
+}
+
 // sdl_batcher_create's refusals of a configuration, made before a device is looked for
 int check_config(const sdl_config *cfg) {
     if (cfg->task != SDL_TASK_MLM && cfg->task != SDL_TASK_CLM && cfg->task != SDL_TASK_MULTI_LABEL &&
@@ -908,8 +996,11 @@ int check_config(const sdl_config *cfg) {
                         "mask_policy 1 / 2 need rng_mode 0: the reference's own draws define no such policy");
     }
     if (cfg->pack != 0 && cfg->pack != 1) return fail(SDL_ERR_ARG, "pack must be 0 (off) or 1 (packed rows)");
-    if (cfg->pack == 1 && cfg->task != SDL_TASK_CLM && cfg->task != SDL_TASK_MLM)
-        return fail(SDL_ERR_ARG, "pack = 1 applies to the CLM and MLM tasks only");
+    if (cfg->pack == 1 && cfg->task != SDL_TASK_CLM && cfg->task != SDL_TASK_MLM && cfg->task != SDL_TASK_SPAN)
+        return fail(SDL_ERR_ARG, "pack = 1 applies to the CLM, MLM and span tasks only");
+    if (cfg->pack == 1 && cfg->task == SDL_TASK_SPAN && cfg->span_policy != SDL_SPAN_T5)
+        return fail(SDL_ERR_ARG, "pack = 1 under the span task needs span_policy 1: the reference's rule defines "
+                                 "nothing for packed rows");
     if (cfg->span_policy < SDL_SPAN_REFERENCE || cfg->span_policy > SDL_SPAN_T5)
         return fail(SDL_ERR_ARG, "span_policy must be 0 (reference) or 1 (T5)");
     if (cfg->span_policy == SDL_SPAN_T5) {
@@ -921,6 +1012,7 @@ int check_config(const sdl_config *cfg) {
         if (cfg->rng_mode == 1)
             return fail(SDL_ERR_UNSUPPORTED,
                         "span_policy 1 needs rng_mode 0: the reference's own draws define no such policy");
+        if (cfg->pack == 1) return pack_span_length(cfg, nullptr);  // (the chunk's capacity rule in the full row's place)
         // the full row is the worst case: t, m and t + m never decrease with n
         int t = 0, m = 0;
         const int S = cfg->sequence_length, LW = S / 4;
@@ -1081,8 +1173,10 @@ void fill_row_params(sdl_batcher *h) {
             P.zig_f = h->d_zig.p + 257;
         }
         if (cfg->span_policy == SDL_SPAN_T5) {  // the counts' one double step stays on the host
-            std::vector<uint32_t> tab((size_t)cfg->sequence_length + 1);
-            span_noise_table(cfg->sequence_length, cfg->span_noise_per_mille, cfg->avg_span_size, tab.data());
+            // (0..S; packed rows: 0..N, the chunk length)
+            const int top = h->pack_span_N > 0 ? h->pack_span_N : cfg->sequence_length;
+            std::vector<uint32_t> tab((size_t)top + 1);
+            span_noise_table(top, cfg->span_noise_per_mille, cfg->avg_span_size, tab.data());
             h->snoise.counts = h->d_span_counts.upload(tab);
         }
     }
@@ -1229,6 +1323,20 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
     if (!cfg || !tokenizer_path || !out) return fail(SDL_ERR_ARG, "null argument");
     *out = nullptr;
     if (int rc = check_config(cfg)) return rc;
+    // (packed span rows: the tokenizer is a host load, so its refusal names pack with or without a device)
+    std::unique_ptr<HostTokenizer> tok_early;
+    if (cfg->pack == 1 && cfg->task == SDL_TASK_SPAN) {
+        const int rc = guarded(SDL_ERR_IO, SDL_ERR_IO, [&]() -> int {
+            tok_early.reset(new HostTokenizer());
+            load_tokenizer(tokenizer_path, data_dir ? std::string(data_dir) : default_data_dir(), *tok_early);
+            if (tok_early->kind != TOK_UNIGRAM || tok_early->eos_id < 0)
+                return fail(SDL_ERR_UNSUPPORTED,
+                            "pack = 1 under the span task needs the t5 (Unigram) tokenizer with a </s> id: packed span "
+                            "rows are not built for WordPiece or byte-level BPE tokenizers");
+            return SDL_OK;
+        });
+        if (rc) return rc;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(SDL_ERR_NODEV, "no HIP device visible: the Batcher runs only on the GPU (no CPU fallback)");
@@ -1237,7 +1345,11 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
     return guarded(SDL_ERR_IO, SDL_ERR_IO, [&]() -> int {
         h->cfg = *cfg;
         h->device = cfg->device;
-        load_tokenizer(tokenizer_path, data_dir ? std::string(data_dir) : default_data_dir(), h->tok);
+        if (tok_early) h->tok = std::move(*tok_early);
+        else load_tokenizer(tokenizer_path, data_dir ? std::string(data_dir) : default_data_dir(), h->tok);
+        if (cfg->pack == 1 && cfg->task == SDL_TASK_SPAN) {
+            if (int rc = pack_span_length(cfg, &h->pack_span_N)) return rc;
+        }
         // (mlm sentence pairs first, so that the refusal names them also under mask_policy 2)
         if (cfg->pair >= SDL_PAIR_MLM && (h->tok.kind != TOK_WORDPIECE || h->tok.cls_id < 0 || h->tok.sep_id < 0))
             return fail(SDL_ERR_UNSUPPORTED,
@@ -1271,7 +1383,11 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
         upload_tables(h.get());
         fill_row_params(h.get());
         if (h->pack()) {  // an empty carry in both halves
-            h->pk_carry.ensure(4 * (size_t)h->P.S);
+            h->pk_carry.ensure(h->pack_span() ? 2 * (((size_t)h->pack_span_N + 3) & ~(size_t)3) : 4 * (size_t)h->P.S);
+            if (h->pack_span()) {  // (d_label_errors: no row of an accepted config is refused -- the word stays 0)
+                h->span_err.ensure(1);
+                HIP_TRY(hipMemsetAsync(h->span_err.p, 0, sizeof(uint32_t), h->stream));
+            }
             h->pk_meta.ensure(sdl_batcher::PK_META_WORDS);
             HIP_TRY(hipMemsetAsync(h->pk_meta.p, 0, sdl_batcher::PK_META_WORDS * sizeof(uint32_t), h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));  // (the first call may come on a caller's stream)
@@ -1468,7 +1584,19 @@ int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out) {
     });
 }
 
-const int32_t *sdl_device_position_ids(sdl_batcher *h) { return h && h->pack() && h->pk_ran ? h->o_tt.p : nullptr; }
+const int32_t *sdl_device_position_ids(sdl_batcher *h) {
+    return h && h->pack() && !h->pack_span() && h->pk_ran ? h->o_tt.p : nullptr;
+}
+
+int sdl_pack_span_length(const sdl_config *cfg) {
+    if (!cfg) return fail(SDL_ERR_ARG, "null argument");
+    if (cfg->pack != 1 || cfg->task != SDL_TASK_SPAN)
+        return fail(SDL_ERR_ARG, "sdl_pack_span_length needs a config with pack = 1 and the span task");
+    if (int rc = check_config(cfg)) return rc;
+    int N = 0;
+    if (int rc = pack_span_length(cfg, &N)) return rc;
+    return N;
+}
 
 const int32_t *sdl_device_pair_labels(sdl_batcher *h) {
     return h && h->pair_mlm() && h->pair_lab_ran ? h->o_pair_lab.p : nullptr;
@@ -1559,6 +1687,10 @@ int sdl_multi_create(const sdl_config *cfg, const char *tokenizer_path, const ch
     if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM)
         return fail(SDL_ERR_UNSUPPORTED,
                     "sdl_multi_create with pack = 1 under the MLM task: every shard would mask its rows with the same "
+                    "packed indices; give each shard's handle its own seed");
+    if (cfg->pack == 1 && cfg->task == SDL_TASK_SPAN)
+        return fail(SDL_ERR_UNSUPPORTED,
+                    "sdl_multi_create with pack = 1 under the span task: every shard would cut its rows with the same "
                     "packed indices; give each shard's handle its own seed");
     std::unique_ptr<sdl_multi> m(new sdl_multi());
     m->next_record = cfg->first_record;

@@ -31,7 +31,7 @@ EXPORTS = [
     "sdl_config_default", "sdl_batcher_create", "sdl_batcher_destroy", "sdl_batcher_push",
     "sdl_batcher_push_many", "sdl_batcher_next", "sdl_batcher_flush", "sdl_batch_release",
     "sdl_batcher_push_pair", "sdl_batcher_push_many_pairs", "sdl_process_device_pairs",
-    "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids",
+    "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids", "sdl_pack_span_length",
     "sdl_batch_pair_labels", "sdl_device_pair_labels",
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
@@ -48,7 +48,7 @@ class SDLError(RuntimeError):
 
 
 class _PackWord(ctypes.Structure):
-    _fields_ = [("pack", ctypes.c_int32),  # clm: 1 = documents concatenated and cut into full rows
+    _fields_ = [("pack", ctypes.c_int32),  # clm / mlm: 1 = documents concatenated and cut into full rows; span: into chunks that fill a row
                 # span: SDL_SPAN_*; policy 1: noise ids per 1000 ids of a row (the header's reserved[0], [1])
                 ("span_policy", ctypes.c_int32), ("span_noise_per_mille", ctypes.c_int32),
                 # SDL_PAIR_*: 1 = two texts per example in one [CLS] A [SEP] B [SEP] row (single-class /
@@ -223,6 +223,8 @@ def load(path=LIB_PATH):
     L.sdl_pack_flush_device.restype = i64
     L.sdl_device_position_ids.argtypes = [vp]
     L.sdl_device_position_ids.restype = vp
+    L.sdl_pack_span_length.argtypes = [ctypes.POINTER(Config)]
+    L.sdl_pack_span_length.restype = i64
     L.sdl_batch_pair_labels.argtypes = [ctypes.POINTER(Batch)]
     L.sdl_batch_pair_labels.restype = ctypes.POINTER(ctypes.c_int32)
     L.sdl_device_pair_labels.argtypes = [vp]

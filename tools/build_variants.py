@@ -30,6 +30,7 @@ DIAG_MACROS = {
     # packed mlm rows: 1 = no pick and no draws, 2 = also no list reads (rows not the contract's):
     # where k_pack_mlm_rows' time goes (build.build_pack_mlm_ablations, var/pack_mlm_abl{1,2})
     "SDL_PACK_MLM_ABLATE": "k_pack_mlm_rows without its pick / its list reads",
+    "SDL_PACK_SPAN_ABLATE": "k_pack_span_rows without Philox / without its keys and selection",
 }
 
 
