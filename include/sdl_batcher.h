@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 /* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device, the three sentence-pair calls, the
- * two pair-label accessors and sdl_pack_span_length were added without changing any existing call
+ * two pair-label accessors, sdl_pack_span_length and sdl_batcher_set_fim were added without changing any existing call
  * or struct (an additive change keeps the version). */
 #define SDL_ABI_VERSION 9
 
@@ -380,6 +380,48 @@ const int32_t *sdl_device_position_ids(sdl_batcher *h);
  * ("Packed span rows" above), or a negative SDL_ERR_* with sdl_last_error set when
  * sdl_batcher_create would refuse the config's words.  Host only: needs no GPU. */
 int sdl_pack_span_length(const sdl_config *cfg);
+
+/* ---- Fill-in-the-middle (packed clm rows; Bavarian et al. 2022, SantaCoder / StarCoder, Code
+ * Llama, DeepSeek-Coder) ----
+ * A setting of a pack = 1, task clm handle, made after sdl_batcher_create (sdl_config is full).
+ * With t the n tokenizer ids of record r: whether r is kept is decided as under "Packed rows"
+ * (n >= 1 and n + 1 >= min_ids), before any draw.  A kept record has the index
+ *     d = first_record + (records given to the handle before it, kept or not)
+ * -- the handle counts its records on the device, so the rows of any split of a record list into
+ * calls are the rows of one call, bit for bit; first_record is the call's (sdl_process_device) or
+ * the config's (host path), and unlike plain packed clm the seed and first_record are used.
+ * Document d takes one Philox4x32-10 block, key (seed lo, seed hi), counter (0, 0x90000000, d lo,
+ * d hi), words x0..x3:
+ *     transformed   x0 * 1000 < rate_per_mille * 2^32   (64-bit: 1000 is always, 0 never)
+ *     cuts          c1 = umulhi(x1, n + 1), c2 = umulhi(x2, n + 1), a = min, b = max:
+ *                   prefix = t[0:a], middle = t[a:b], suffix = t[b:n]; any of them may be empty
+ *     SPM order     x3 * 1000 < spm_per_mille * 2^32
+ * and its segment of the stream is
+ *     untouched   t ++ [eos]                                                          n + 1 ids
+ *     PSM         [PRE] ++ prefix ++ [SUF] ++ suffix ++ [MID] ++ middle ++ [eos]      n + 4
+ *     SPM         [PRE, SUF] ++ suffix ++ [MID] ++ prefix ++ middle ++ [eos]          n + 4
+ * (SPM is Bavarian's variant 2, the one BigCode trains).  Rows, carry, flush row, padding rows,
+ * labels = input_ids, attention_mask and position_ids (restarting at each row start and after each
+ * document's eos) are those of "Packed rows" over this stream; the carry holds transformed ids, so
+ * a document cut by a call boundary finishes from the carry alone.  d_record_rows[r] is the
+ * segment length (n + 1, n + 4, or 0 when dropped) and rows_capacity = (ids + 4 R + S - 1) / S + 1
+ * rounded up to B.  The three sentinel ids are the caller's: the tokenizer never emits them for any
+ * text and never parses them from text (GPT-2's vocabulary has no FIM pieces; reserve ids as
+ * StarCoder's and SantaCoder's vocabularies do).  Document-level FIM only: no context-level variant
+ * (after the cut into rows), no character-level cuts, no truncation rule. */
+typedef struct sdl_fim {
+    int32_t rate_per_mille;  /* documents transformed per 1000, 0..1000 (0 = none) */
+    int32_t spm_per_mille;   /* of the transformed ones, those in suffix-prefix-middle order, 0..1000 */
+    int32_t prefix_id, suffix_id, middle_id;  /* the three sentinel ids, each in [0, vocabulary size), distinct,
+                                                 none equal to the end-of-text id */
+    int32_t reserved[3];     /* must be 0 */
+} sdl_fim;
+/* Accepts only a handle created with pack = 1 and task clm that has seen no record yet (no push, no
+ * sdl_process_device* call, no flush): SDL_ERR_STATE otherwise, naming the rule.  A value out of
+ * range, sentinel ids that are not distinct or equal the end-of-text id, and non-zero reserved
+ * words: SDL_ERR_ARG naming the field.  A shard of an sdl_multi: SDL_ERR_UNSUPPORTED.  Without this
+ * call a handle's rows and launches are what they were. */
+int sdl_batcher_set_fim(sdl_batcher *h, const sdl_fim *fim);
 
 /* sdl_process_device for the multi-label task with Label::Multi indices per
  * record: record r's indices are d_labels[d_label_offsets[r] .. d_label_offsets[r+1])

@@ -48,10 +48,25 @@ class Mask:
 
 
 @dataclass
+class Fim:
+    """sdl_fim (DESIGN.md §3 "Fill-in-the-middle"): rate_per_mille of a packed clm handle's documents
+    enter the stream as <PRE> prefix <SUF> suffix <MID> middle, spm_per_mille of those in the
+    suffix-prefix-middle order; the three sentinel ids are the caller's (the tokenizer never emits
+    or parses them)."""
+    rate_per_mille: int
+    spm_per_mille: int
+    prefix_id: int
+    suffix_id: int
+    middle_id: int
+
+
+@dataclass
 class Gpt:
     # sdl_config.pack (DESIGN.md §3 "Packed rows"): documents concatenated with the end-of-text id
     # and the stream cut into full rows, with a position_ids plane; off = the reference's rows
     pack: bool = False
+    # pack only: fill-in-the-middle documents (sdl_batcher_set_fim, applied right after create)
+    fim: Optional[Fim] = None
 
 
 @dataclass
@@ -340,6 +355,8 @@ class _NativeBatcher(Batcher):
         self._h = h
         self._destroy = L.sdl_batcher_destroy  # bound now: close() may run at interpreter teardown
         native.track(self)
+        if getattr(dataset_config, "fim", None) is not None:
+            native.set_fim(self._h, dataset_config.fim)
         self.batch_config = batch_config
         self.dataset_config = dataset_config
         # mlm sentence pairs: the key DataSet.to_dict() files the pair labels under (the frames' fifth key)

@@ -517,6 +517,14 @@ struct sdl_batcher {
     PackParams pack_params(int64_t R, int64_t rows_cap);
     void run_pack(int64_t R, int64_t rows_cap, hipStream_t st);
     void run_pack_flush(hipStream_t st);
+    // sdl_batcher_set_fim (pack_fim.hip): the setting, a plan word per record of the call, and the
+    // records the handle has seen as one 64-bit counter in pk_meta[4..5] (packed clm has no row
+    // counter there); k_pack_carry_fim advances it by R on the stream, the flush leaves it
+    bool fim_on = false;
+    sdl_fim fim{};
+    bool in_multi = false;  // a shard of an sdl_multi: sdl_batcher_set_fim refuses it
+    DevBuf<uint2> pk_plan;
+    void run_pack_fim(int64_t R, int64_t rows_cap, uint64_t first_record, hipStream_t st);
     DevBuf<uint32_t> pair_rb;  // pair != 0: the one segment's record bounds {0, n_pairs}
     DevBuf<int32_t> o_pair_lab;  // pair 2..4: the pair label of every row of the last call, grown with the row planes
     bool pair_lab_ran = false;   // ... written by a call (sdl_device_pair_labels is NULL before)

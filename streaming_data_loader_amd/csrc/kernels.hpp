@@ -434,6 +434,38 @@ hipError_t launch_pack_rows(const PackParams &q, hipStream_t st);
 // the carry as one last row (0 rows when it is empty), rows < B of the planes; the new carry is empty
 hipError_t launch_pack_flush(const PackParams &q, hipStream_t st);
 
+// pack_fim.hip: pack.hip's rows with fill-in-the-middle documents (sdl_batcher_set_fim, DESIGN.md §3
+// "Fill-in-the-middle"): a drawn share of the documents enters the stream as
+// <PRE> prefix <SUF> suffix <MID> middle (or the suffix-prefix-middle order) with three sentinel ids,
+// permuted inside the gather.  A struct and kernels of their own again: k_pack_lengths,
+// k_pack_gather and k_pack_carry compile to what they were; k_pack_flush serves both (the carry
+// holds transformed ids).
+constexpr uint32_t FIM_DOMAIN = 0x90000000u;  // word 1 of the draw's Philox counter (0, FIM_DOMAIN, d lo, d hi)
+constexpr uint32_t FIM_FLAG = 0x80000000u;    // plan.x: the document is transformed; plan.y: in SPM order
+struct PackFimParams {
+    const uint32_t *tok, *rec_tok, *rec_cnt;  // the dense ids and each record's first id / id count
+    uint32_t *rec_len;                        // out [R]: stream positions record r adds (n + 1, n + 4, 0 = dropped)
+    uint32_t *pk_off;                         // [R + 1]: where record r starts in the call's stream; [R] = its length
+    uint2 *plan;                              // [R]: {a | FIM_FLAG, b | spm FIM_FLAG} of a transformed record, else {0, 0}
+    int64_t R, rows_cap;                      // rows_cap * S < 2^32
+    uint64_t seed, first_record;              // the Philox key; record r draws as d = first_record + *rec_seen + r
+    int32_t S, B, eos, min_ids;
+    int32_t rate, spm, pre, suf, mid, pad;    // sdl_fim: the two per-mille rates and the three sentinel ids
+    const int32_t *carry_ids, *carry_pos;     // the carry the last call left (< S transformed ids and their position_ids)
+    const uint32_t *carry_len;
+    int32_t *new_ids, *new_pos;               // the other half of the double buffer: this call's carry
+    uint32_t *new_len;
+    uint64_t *rec_seen;                       // records given to the handle before this call; k_pack_carry_fim adds R
+    int32_t *ids, *am, *lab, *pos;            // planes [rows_cap, S]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// in launch_pack_lengths' place: the draws, plan and rec_len, and pk_off[0] = the carry length; then
+// launch_exclusive_scan(rec_len, pk_off, R, tmp, st, pk_off) as for the plain rows
+hipError_t launch_fim_plan(const PackFimParams &q, hipStream_t st);
+// the four planes (the gather over the flat output index, through the element map), then the new
+// carry, its length, the record counter and d_rows
+hipError_t launch_pack_fim_rows(const PackFimParams &q, hipStream_t st);
+
 // pack_mlm.hip: MLM rows packed from the stream of [CLS] ids [SEP] documents with a BERT masking policy
 // applied to every full row (sdl_config.pack = 1 under the MLM task, DESIGN.md §3 "Packed rows"),
 // after launch_records, launch_pack_lengths(.., 2) and the seeded scan into pk_off.  A struct of its

@@ -83,6 +83,50 @@ void sdl_batcher::run_pack(int64_t R, int64_t rows_cap, hipStream_t st) {
     pk_cur ^= 1;
     pk_ran = true;
 }
+// fill-in-the-middle (sdl_batcher_set_fim): the plan kernel in launch_pack_lengths' place, the same
+// scan, the gather and carry kernels that read the ids through the plan -- no host synchronisation
+void sdl_batcher::run_pack_fim(int64_t R, int64_t rows_cap, uint64_t first_record, hipStream_t st) {
+    pk_off.ensure((size_t)R + 1);
+    pk_plan.ensure((size_t)std::max<int64_t>(R, 1));
+    const PackParams c = pack_params(R, rows_cap);
+    PackFimParams q{};
+    q.tok = c.tok;
+    q.rec_tok = c.rec_tok;
+    q.rec_cnt = c.rec_cnt;
+    q.rec_len = c.rec_len;
+    q.pk_off = c.pk_off;
+    q.plan = pk_plan.p;
+    q.R = R;
+    q.rows_cap = rows_cap;
+    q.seed = P.seed;
+    q.first_record = first_record;
+    q.S = c.S;
+    q.B = c.B;
+    q.eos = c.eos;
+    q.min_ids = c.min_ids;
+    q.rate = fim.rate_per_mille;
+    q.spm = fim.spm_per_mille;
+    q.pre = fim.prefix_id;
+    q.suf = fim.suffix_id;
+    q.mid = fim.middle_id;
+    q.carry_ids = c.carry_ids;
+    q.carry_pos = c.carry_pos;
+    q.carry_len = c.carry_len;
+    q.new_ids = c.new_ids;
+    q.new_pos = c.new_pos;
+    q.new_len = c.new_len;
+    q.rec_seen = reinterpret_cast<uint64_t *>(pk_meta.p + 4);
+    q.ids = c.ids;
+    q.am = c.am;
+    q.lab = c.lab;
+    q.pos = c.pos;
+    q.d_rows = c.d_rows;
+    HIP_TRY(launch_fim_plan(q, st));
+    HIP_TRY(launch_exclusive_scan(rec_rows.p, pk_off.p, R, scan_tmp.p, st, pk_off.p));
+    HIP_TRY(launch_pack_fim_rows(q, st));
+    pk_cur ^= 1;
+    pk_ran = true;
+}
 // packed mlm: the same carry buffers, the row counter beside the carry lengths, the chunk lists in
 // the place of the dense ids and the token types in a plane of their own
 PackMlmParams sdl_batcher::pack_mlm_params(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off) {
@@ -286,6 +330,7 @@ int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     const int64_t ids = dt.kind == TOK_UNIGRAM ? 2 * N + 1024 * 1024 : N;
     int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
     if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
+    if (fim_on) cap = (ids + 4 * R + P.S - 1) / P.S + 1;  // ... + three sentinels per record (fill-in-the-middle)
     if (pack_mlm()) cap = (ids + 2 * R + P.S - 1) / P.S + 1;  // ... + a [CLS] and a [SEP] per record
     if (pack_span()) cap = (ids + R + pack_span_N - 1) / pack_span_N + 1;  // chunks of N ids: carry (< N) + ids + a </s> per record
     if (pair()) cap = R / 2;                          // a row per pair of text ranges
@@ -464,6 +509,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
             mark(6);
             if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
             else if (pack_span()) run_pack_span(R, rows_cap, s);
+            else if (fim_on) run_pack_fim(R, rows_cap, first_record, s);
             else run_pack(R, rows_cap, s);
             return;
         }
@@ -728,8 +774,10 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
             FusedH2D &f;
             ~Clear() { f = FusedH2D{}; }
         } clear{fused_h2d};
-        run_device(d_text, N, d_off, R, first_override >= 0 ? (uint64_t)first_override : cfg.first_record + n_records,
-                   stream, d_labels, d_label_off);
+        // (fill-in-the-middle: the handle counts its records on the device, beside first_record)
+        run_device(d_text, N, d_off, R,
+                   first_override >= 0 ? (uint64_t)first_override : cfg.first_record + (fim_on ? 0 : n_records), stream,
+                   d_labels, d_label_off);
     }
     fuse_stat = nullptr;
     if (pack()) {  // the stream's rows fill the queue's batches; no per-record cadence
@@ -1584,6 +1632,35 @@ int sdl_pack_flush_device(sdl_batcher *h, void *stream, sdl_device_rows *out) {
     });
 }
 
+int sdl_batcher_set_fim(sdl_batcher *h, const sdl_fim *f) {
+    if (!h || !f) return fail(SDL_ERR_ARG, "null argument");
+    if (!h->pack() || h->P.task != SDL_TASK_CLM)
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_fim needs a handle created with pack = 1 under the CLM task: "
+                                   "fill-in-the-middle is defined for packed clm rows only");
+    if (h->in_multi)
+        return fail(SDL_ERR_UNSUPPORTED, "sdl_batcher_set_fim on a shard of an sdl_multi: the draw's record index is "
+                                         "counted per handle; give each shard a handle of its own");
+    if (h->pk_ran || h->n_records > 0)
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_fim after the handle has seen a record: set it right after "
+                                   "sdl_batcher_create, before any push, sdl_process_device or flush");
+    if (f->rate_per_mille < 0 || f->rate_per_mille > 1000) return fail(SDL_ERR_ARG, "sdl_fim.rate_per_mille must be 0..1000");
+    if (f->spm_per_mille < 0 || f->spm_per_mille > 1000) return fail(SDL_ERR_ARG, "sdl_fim.spm_per_mille must be 0..1000");
+    const int32_t vocab = (int32_t)h->tok.pieces.size(), sent[3] = {f->prefix_id, f->suffix_id, f->middle_id};
+    const char *names[3] = {"sdl_fim.prefix_id", "sdl_fim.suffix_id", "sdl_fim.middle_id"};
+    for (int k = 0; k < 3; ++k) {
+        if (sent[k] < 0 || sent[k] >= vocab)
+            return fail(SDL_ERR_ARG, std::string(names[k]) + " must lie in [0, " + std::to_string(vocab) + "), the vocabulary");
+        if (sent[k] == h->tok.eos_id) return fail(SDL_ERR_ARG, std::string(names[k]) + " equals the end-of-text id");
+        for (int j = 0; j < k; ++j)
+            if (sent[k] == sent[j]) return fail(SDL_ERR_ARG, std::string(names[k]) + " equals " + names[j] + ": the three sentinel ids must be distinct");
+    }
+    for (int k = 0; k < 3; ++k)
+        if (f->reserved[k] != 0) return fail(SDL_ERR_ARG, "sdl_fim.reserved must be 0");
+    h->fim = *f;
+    h->fim_on = true;
+    return SDL_OK;
+}
+
 const int32_t *sdl_device_position_ids(sdl_batcher *h) {
     return h && h->pack() && !h->pack_span() && h->pk_ran ? h->o_tt.p : nullptr;
 }
@@ -1699,6 +1776,7 @@ int sdl_multi_create(const sdl_config *cfg, const char *tokenizer_path, const ch
         c.device = devices[k];
         sdl_batcher *h = nullptr;
         if (int rc = sdl_batcher_create(&c, tokenizer_path, data_dir, &h)) return rc;
+        h->in_multi = true;
         m->h.push_back(h);
     }
     *out = m.release();

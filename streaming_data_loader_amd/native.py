@@ -32,7 +32,7 @@ EXPORTS = [
     "sdl_batcher_push_many", "sdl_batcher_next", "sdl_batcher_flush", "sdl_batch_release",
     "sdl_batcher_push_pair", "sdl_batcher_push_many_pairs", "sdl_process_device_pairs",
     "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids", "sdl_pack_span_length",
-    "sdl_batch_pair_labels", "sdl_device_pair_labels",
+    "sdl_batch_pair_labels", "sdl_device_pair_labels", "sdl_batcher_set_fim",
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
     "sdl_gzip_inflate_device", "sdl_gzip_inflate_first_device", "sdl_gzip_split_members", "sdl_build_id",
@@ -97,6 +97,15 @@ class DeviceRows(ctypes.Structure):
         ("d_record_rows", ctypes.c_void_p), ("d_tokens", ctypes.c_void_p),
         ("rows_capacity", ctypes.c_uint64), ("label_width", ctypes.c_int32),
         ("d_label_errors", ctypes.c_void_p), ("d_tokenize_errors", ctypes.c_void_p),
+    ]
+
+
+class Fim(ctypes.Structure):
+    """sdl_fim: fill-in-the-middle documents in packed clm rows (sdl_batcher_set_fim)."""
+    _fields_ = [
+        ("rate_per_mille", ctypes.c_int32), ("spm_per_mille", ctypes.c_int32),
+        ("prefix_id", ctypes.c_int32), ("suffix_id", ctypes.c_int32), ("middle_id", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -225,6 +234,8 @@ def load(path=LIB_PATH):
     L.sdl_device_position_ids.restype = vp
     L.sdl_pack_span_length.argtypes = [ctypes.POINTER(Config)]
     L.sdl_pack_span_length.restype = i64
+    L.sdl_batcher_set_fim.argtypes = [vp, ctypes.POINTER(Fim)]
+    L.sdl_batcher_set_fim.restype = i64
     L.sdl_batch_pair_labels.argtypes = [ctypes.POINTER(Batch)]
     L.sdl_batch_pair_labels.restype = ctypes.POINTER(ctypes.c_int32)
     L.sdl_device_pair_labels.argtypes = [vp]
@@ -295,6 +306,15 @@ def default_config(task):
     c = Config()
     load().sdl_config_default(ctypes.byref(c), task)
     return c
+
+
+def set_fim(handle, fim):
+    """sdl_batcher_set_fim on a fresh pack = 1 clm handle.  `fim`: a native.Fim, or any object with
+    rate_per_mille, spm_per_mille, prefix_id, suffix_id and middle_id (batcher.Fim)."""
+    if not isinstance(fim, Fim):
+        fim = Fim(int(fim.rate_per_mille), int(fim.spm_per_mille), int(fim.prefix_id), int(fim.suffix_id),
+                  int(fim.middle_id))
+    check(load().sdl_batcher_set_fim(handle, ctypes.byref(fim)))
 
 
 def shard_records(offsets, n_shards):
