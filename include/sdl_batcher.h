@@ -33,8 +33,9 @@ extern "C" {
 #endif
 
 /* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device, the three sentence-pair calls, the
- * two pair-label accessors, sdl_pack_span_length and sdl_batcher_set_fim were added without changing any existing call
- * or struct (an additive change keeps the version). */
+ * two pair-label accessors, sdl_pack_span_length, sdl_batcher_set_fim and sdl_batcher_set_best_fit
+ * (with sdl_best_fit) were added without changing any existing call or struct (an additive change
+ * keeps the version). */
 #define SDL_ABI_VERSION 9
 
 enum {
@@ -422,6 +423,50 @@ typedef struct sdl_fim {
  * words: SDL_ERR_ARG naming the field.  A shard of an sdl_multi: SDL_ERR_UNSUPPORTED.  Without this
  * call a handle's rows and launches are what they were. */
 int sdl_batcher_set_fim(sdl_batcher *h, const sdl_fim *fim);
+
+/* ---- Best-fit rows (packed clm rows; Ding et al., "Fewer Truncations Improve Language Modeling",
+ * ICML 2024; TRL's packing_strategy="bfd") ----
+ * A setting of a pack = 1, task clm handle, made after sdl_batcher_create (sdl_config is full).
+ * No document shorter than a row is cut.  With t_r the n_r tokenizer ids of record r of a call:
+ * whether r is kept is decided as under "Packed rows" (n_r >= 1 and n_r + 1 >= min_ids), and a kept
+ * record's segment is t_r ++ [eos], L_r = n_r + 1 ids.
+ *   windows    window k of a call is records [k W, (k + 1) W) of that call, W = window_records;
+ *              dropped records count toward W; the last window may be short.  Each window is packed
+ *              on its own and the windows emit their rows in window order.
+ *   pieces     a segment of L ids gives floor(L / S) full pieces of S ids and, when L mod S > 0,
+ *              one tail of L mod S ids; piece c is segment[c S, ...).
+ *   full rows  a window's rows start with its full pieces, one row each, in (record, piece) order.
+ *   tail rows  the window's tails are then taken in order of decreasing length, equal lengths by
+ *              ascending record index.  A tail goes into the open row with the least free room that
+ *              is >= its length; among open rows with exactly that room, into the one that came to
+ *              have that room most recently (a stack per room value); when no open row has room, a
+ *              new row is opened behind the window's rows so far.  Open rows are the rows opened by
+ *              tails of this window: full rows have room 0 and never take a tail.
+ *   a row      its pieces lie in placement order from column 0.  Over a piece input_ids = labels =
+ *              the ids (the eos belongs to its document) and attention_mask = 1; position_ids
+ *              restarts at 0 at each piece's first column (the rule of "Packed rows", where a row
+ *              start restarts it too).  Columns behind the last piece hold the flush row's values:
+ *              input_ids 0, attention_mask 0, labels -100, position_ids 0.  Rows from *d_rows to the
+ *              next multiple of B hold the clm padding rows' values, as under "Packed rows".
+ * There is no carry: sdl_pack_flush_device gives *d_rows = 0 and sdl_batcher_flush only pops the
+ * queue.  The rows therefore depend on how the record list is cut into calls, and on W -- as the
+ * NSP draw's partner does: a caller who needs the same rows again keeps its calls the same.
+ * sdl_batcher_push is a call of one record, a window of one.  The seed and first_record are unused.
+ * d_record_rows[r] stays L_r (0 when dropped), d_tokens stays as it is, and
+ *     rows_capacity = 2 * ((ids + R + S - 1) / S) + ceil(R / W) + 1, rounded up to B
+ * (best fit leaves at most one open row per window at most half full).  sdl_pickle_frames_device
+ * frames the three clm keys over these planes; sdl_json_to_frames stays SDL_ERR_UNSUPPORTED. */
+typedef struct sdl_best_fit {
+    int32_t window_records;  /* W: records of a call packed together, 1..4096 */
+    int32_t reserved[3];     /* must be 0 */
+} sdl_best_fit;
+/* Accepts only a handle created with pack = 1 and task clm that has seen no record yet and has no
+ * fill-in-the-middle setting: SDL_ERR_STATE otherwise, naming the rule (and sdl_batcher_set_fim
+ * refuses a handle that has best fit set, SDL_ERR_STATE).  sequence_length > 4096 (the rooms of a
+ * row are a 4096-bit map): SDL_ERR_ARG naming sequence_length.  window_records outside 1..4096 and
+ * non-zero reserved words: SDL_ERR_ARG naming the field.  A shard of an sdl_multi:
+ * SDL_ERR_UNSUPPORTED.  Without this call a handle's rows and launches are what they were. */
+int sdl_batcher_set_best_fit(sdl_batcher *h, const sdl_best_fit *bf);
 
 /* sdl_process_device for the multi-label task with Label::Multi indices per
  * record: record r's indices are d_labels[d_label_offsets[r] .. d_label_offsets[r+1])

@@ -61,12 +61,22 @@ class Fim:
 
 
 @dataclass
+class BestFit:
+    """sdl_best_fit (DESIGN.md §3 "Best-fit rows"): a packed clm handle cuts no document shorter than a
+    row; the leftover tails of every window_records records of a call are placed into rows by
+    best-fit-decreasing, with padding behind them."""
+    window_records: int = 1024
+
+
+@dataclass
 class Gpt:
     # sdl_config.pack (DESIGN.md §3 "Packed rows"): documents concatenated with the end-of-text id
     # and the stream cut into full rows, with a position_ids plane; off = the reference's rows
     pack: bool = False
     # pack only: fill-in-the-middle documents (sdl_batcher_set_fim, applied right after create)
     fim: Optional[Fim] = None
+    # pack only, not with fim: best-fit-decreasing rows (sdl_batcher_set_best_fit, applied right after create)
+    best_fit: Optional[BestFit] = None
 
 
 @dataclass
@@ -357,6 +367,8 @@ class _NativeBatcher(Batcher):
         native.track(self)
         if getattr(dataset_config, "fim", None) is not None:
             native.set_fim(self._h, dataset_config.fim)
+        if getattr(dataset_config, "best_fit", None) is not None:
+            native.set_best_fit(self._h, dataset_config.best_fit)
         self.batch_config = batch_config
         self.dataset_config = dataset_config
         # mlm sentence pairs: the key DataSet.to_dict() files the pair labels under (the frames' fifth key)

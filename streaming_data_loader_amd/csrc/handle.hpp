@@ -525,6 +525,15 @@ struct sdl_batcher {
     bool in_multi = false;  // a shard of an sdl_multi: sdl_batcher_set_fim refuses it
     DevBuf<uint2> pk_plan;
     void run_pack_fim(int64_t R, int64_t rows_cap, uint64_t first_record, hipStream_t st);
+    // sdl_batcher_set_best_fit (pack_bestfit.hip): the setting and the call's plan -- per record the
+    // full pieces before it in its window, the open rows' runs and the placed tails; per window its
+    // rows, its full rows and (scanned) its first row.  No carry: the carry lengths in pk_meta stay 0,
+    // so the flush kernel emits no row
+    bool bf_on = false;
+    sdl_best_fit bf{};
+    DevBuf<uint32_t> bf_foff, bf_run, bf_win;
+    DevBuf<uint4> bf_piece;
+    void run_pack_best_fit(int64_t R, int64_t rows_cap, hipStream_t st);
     DevBuf<uint32_t> pair_rb;  // pair != 0: the one segment's record bounds {0, n_pairs}
     DevBuf<int32_t> o_pair_lab;  // pair 2..4: the pair label of every row of the last call, grown with the row planes
     bool pair_lab_ran = false;   // ... written by a call (sdl_device_pair_labels is NULL before)

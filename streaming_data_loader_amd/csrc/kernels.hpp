@@ -466,6 +466,30 @@ hipError_t launch_fim_plan(const PackFimParams &q, hipStream_t st);
 // carry, its length, the record counter and d_rows
 hipError_t launch_pack_fim_rows(const PackFimParams &q, hipStream_t st);
 
+// pack_bestfit.hip: packed CLM rows by best-fit-decreasing (sdl_batcher_set_best_fit, DESIGN.md §3
+// "Best-fit rows"): documents longer than a row are cut into row-sized pieces, every other document
+// and every leftover tail stays whole, and the tails of a window of W records are placed into rows
+// by best fit.  No stream, no carry: a struct and kernels of their own, pack.hip and pack_fim.hip
+// compile to what they were.
+struct BestFitParams {
+    const uint32_t *tok, *rec_tok, *rec_cnt;  // the dense ids and each record's first id / id count
+    uint32_t *rec_len;                        // out [R]: the segment length L_r = n_r + 1 (0 = dropped)
+    uint32_t *foff;                           // [R]: full pieces of the records before r in r's window
+    uint32_t *run;                            // [R] at k W + t: open row t of window k = first piece | pieces << 16
+    uint4 *piece;                             // [R] at k W + d: {column, length, index of its first id in tok, record}
+    uint32_t *win_rows, *win_full;            // [nW]: window k's rows (the scan's input) and its full rows
+    uint32_t *win_off;                        // [nW + 1]: window k's first row; [nW] = the call's rows
+    int64_t R, rows_cap, nW;                  // rows_cap * S < 2^32; nW = max(1, ceil(R / W))
+    int32_t S, B, W, P, eos, min_ids;         // P: a power of two >= the records of a window, >= 64
+    int32_t *ids, *am, *lab, *pos;            // planes [rows_cap, S]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// rec_len, the per-window plan (foff, run, piece) and win_rows / win_full: one wave a window; then
+// launch_exclusive_scan(win_rows, win_off, nW, tmp, st)
+hipError_t launch_bestfit_plan(const BestFitParams &q, hipStream_t st);
+// the four planes row by row, the padding rows up to the next multiple of B, and d_rows = win_off[nW]
+hipError_t launch_bestfit_rows(const BestFitParams &q, hipStream_t st);
+
 // pack_mlm.hip: MLM rows packed from the stream of [CLS] ids [SEP] documents with a BERT masking policy
 // applied to every full row (sdl_config.pack = 1 under the MLM task, DESIGN.md §3 "Packed rows"),
 // after launch_records, launch_pack_lengths(.., 2) and the seeded scan into pk_off.  A struct of its

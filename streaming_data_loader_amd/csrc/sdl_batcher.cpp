@@ -127,6 +127,48 @@ void sdl_batcher::run_pack_fim(int64_t R, int64_t rows_cap, uint64_t first_recor
     pk_cur ^= 1;
     pk_ran = true;
 }
+// best-fit rows (sdl_batcher_set_best_fit): the plan kernel (a wave a window), the scan of the windows'
+// row counts, the row kernel -- launches only, no host synchronisation; the carry stays empty
+void sdl_batcher::run_pack_best_fit(int64_t R, int64_t rows_cap, hipStream_t st) {
+    const int64_t W = bf.window_records, nW = std::max<int64_t>((R + W - 1) / W, 1);
+    int64_t Pw = 64;  // the sort's width: a power of two >= the records of a window
+    while (Pw < std::min(W, R)) Pw *= 2;
+    const size_t n = (size_t)std::max<int64_t>(R, 1);
+    bf_foff.ensure(n);
+    bf_run.ensure(n);
+    bf_piece.ensure(n);
+    bf_win.ensure(3 * (size_t)nW + 1);  // (scan_tmp holds scan_tmp_words(R) already, and nW <= R past one workgroup)
+    const PackParams c = pack_params(R, rows_cap);
+    BestFitParams q{};
+    q.tok = c.tok;
+    q.rec_tok = c.rec_tok;
+    q.rec_cnt = c.rec_cnt;
+    q.rec_len = c.rec_len;
+    q.foff = bf_foff.p;
+    q.run = bf_run.p;
+    q.piece = bf_piece.p;
+    q.win_rows = bf_win.p;
+    q.win_full = bf_win.p + nW;
+    q.win_off = bf_win.p + 2 * nW;
+    q.R = R;
+    q.rows_cap = rows_cap;
+    q.nW = nW;
+    q.S = c.S;
+    q.B = c.B;
+    q.W = (int32_t)W;
+    q.P = (int32_t)Pw;
+    q.eos = c.eos;
+    q.min_ids = c.min_ids;
+    q.ids = c.ids;
+    q.am = c.am;
+    q.lab = c.lab;
+    q.pos = c.pos;
+    q.d_rows = c.d_rows;
+    HIP_TRY(launch_bestfit_plan(q, st));
+    HIP_TRY(launch_exclusive_scan(q.win_rows, q.win_off, nW, scan_tmp.p, st));
+    HIP_TRY(launch_bestfit_rows(q, st));
+    pk_ran = true;
+}
 // packed mlm: the same carry buffers, the row counter beside the carry lengths, the chunk lists in
 // the place of the dense ids and the token types in a plane of their own
 PackMlmParams sdl_batcher::pack_mlm_params(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off) {
@@ -331,6 +373,11 @@ int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
     if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
     if (fim_on) cap = (ids + 4 * R + P.S - 1) / P.S + 1;  // ... + three sentinels per record (fill-in-the-middle)
+    // best fit: the full rows hold S ids each.  Of a window's open rows at most one is at most half
+    // full -- the tail that opened the later of two such rows (<= S / 2 ids, as the row never holds
+    // fewer) would have fitted the earlier one, whose room was >= S / 2 then as now -- so a window
+    // opens fewer than 2 (its tail ids) / S + 1 rows: rows <= 2 (ids + R) / S + ceil(R / W) in all
+    if (bf_on) cap = 2 * ((ids + R + P.S - 1) / P.S) + (R + bf.window_records - 1) / bf.window_records + 1;
     if (pack_mlm()) cap = (ids + 2 * R + P.S - 1) / P.S + 1;  // ... + a [CLS] and a [SEP] per record
     if (pack_span()) cap = (ids + R + pack_span_N - 1) / pack_span_N + 1;  // chunks of N ids: carry (< N) + ids + a </s> per record
     if (pair()) cap = R / 2;                          // a row per pair of text ranges
@@ -510,6 +557,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
             if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
             else if (pack_span()) run_pack_span(R, rows_cap, s);
             else if (fim_on) run_pack_fim(R, rows_cap, first_record, s);
+            else if (bf_on) run_pack_best_fit(R, rows_cap, s);
             else run_pack(R, rows_cap, s);
             return;
         }
@@ -1026,8 +1074,10 @@ int check_config(const sdl_config *cfg) {
         return fail(SDL_ERR_ARG, "span needs sequence_length >= 4 and finite avg_span_gap / avg_span_size");
     if (cfg->task == SDL_TASK_MULTI_LABEL && (cfg->number_labels <= 0 || cfg->number_labels > 4096))
         return fail(SDL_ERR_ARG, "number_labels must be in [1, 4096]");
-    if (cfg->batch_size <= 0 || cfg->sequence_length <= 0 || cfg->sequence_length > 2048)
-        return fail(SDL_ERR_ARG, "batch_size must be > 0 and 0 < sequence_length <= 2048");
+    // (packed clm rows, whose kernels hold no row in LDS or registers, go up to the 4096 of best-fit rows)
+    const int max_S = cfg->pack == 1 && cfg->task == SDL_TASK_CLM ? 4096 : 2048;
+    if (cfg->batch_size <= 0 || cfg->sequence_length <= 0 || cfg->sequence_length > max_S)
+        return fail(SDL_ERR_ARG, "batch_size must be > 0 and 0 < sequence_length <= 2048 (<= 4096 for pack = 1 under the CLM task)");
     if (cfg->task == SDL_TASK_MLM && (cfg->mask_length < 0 || cfg->mask_length > cfg->sequence_length))
         return fail(SDL_ERR_ARG, "mask_length must be in [0, sequence_length]");
     if (cfg->rng_mode != 0 && cfg->rng_mode != 1) return fail(SDL_ERR_ARG, "rng_mode must be 0 or 1");
@@ -1545,6 +1595,7 @@ int sdl_batcher_flush(sdl_batcher *h, sdl_batch *out) {
         // the carry becomes the flush row behind the queued rows; then the front of the queue:
         // the full batches first, the partial one last, nothing once no filled row is left
         const int rc = guarded(SDL_ERR_ARG, SDL_ERR_ARG, [&]() -> int {
+            if (h->bf_on) return SDL_OK;  // best-fit rows: no carry, every row is queued already
             h->run_pack_flush(h->stream);
             h->queue_packed_rows();
             return SDL_OK;
@@ -1640,6 +1691,9 @@ int sdl_batcher_set_fim(sdl_batcher *h, const sdl_fim *f) {
     if (h->in_multi)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_batcher_set_fim on a shard of an sdl_multi: the draw's record index is "
                                          "counted per handle; give each shard a handle of its own");
+    if (h->bf_on)
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_fim on a handle that has best fit set: best-fit rows with "
+                                   "fill-in-the-middle documents are not built");
     if (h->pk_ran || h->n_records > 0)
         return fail(SDL_ERR_STATE, "sdl_batcher_set_fim after the handle has seen a record: set it right after "
                                    "sdl_batcher_create, before any push, sdl_process_device or flush");
@@ -1658,6 +1712,32 @@ int sdl_batcher_set_fim(sdl_batcher *h, const sdl_fim *f) {
         if (f->reserved[k] != 0) return fail(SDL_ERR_ARG, "sdl_fim.reserved must be 0");
     h->fim = *f;
     h->fim_on = true;
+    return SDL_OK;
+}
+
+int sdl_batcher_set_best_fit(sdl_batcher *h, const sdl_best_fit *bf) {
+    if (!h || !bf) return fail(SDL_ERR_ARG, "null argument");
+    if (!h->pack() || h->P.task != SDL_TASK_CLM)
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_best_fit needs a handle created with pack = 1 under the CLM task: "
+                                   "best-fit rows are defined for packed clm rows only");
+    if (h->in_multi)
+        return fail(SDL_ERR_UNSUPPORTED, "sdl_batcher_set_best_fit on a shard of an sdl_multi: the windows are cut "
+                                         "from one handle's calls; give each shard a handle of its own");
+    if (h->fim_on)
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_best_fit on a handle that has fill-in-the-middle set: best-fit "
+                                   "rows with fill-in-the-middle documents are not built");
+    if (h->pk_ran || h->n_records > 0)
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_best_fit after the handle has seen a record: set it right after "
+                                   "sdl_batcher_create, before any push, sdl_process_device or flush");
+    if (h->P.S > 4096)
+        return fail(SDL_ERR_ARG, "sdl_batcher_set_best_fit: sequence_length must be <= 4096 (the rooms of a row are "
+                                 "a 4096-bit map)");
+    if (bf->window_records < 1 || bf->window_records > 4096)
+        return fail(SDL_ERR_ARG, "sdl_best_fit.window_records must be 1..4096");
+    for (int k = 0; k < 3; ++k)
+        if (bf->reserved[k] != 0) return fail(SDL_ERR_ARG, "sdl_best_fit.reserved must be 0");
+    h->bf = *bf;
+    h->bf_on = true;
     return SDL_OK;
 }
 

@@ -165,7 +165,8 @@ class DeviceBatcher:
     def __init__(self, task=native.SDL_TASK_MLM, batch_size=256, sequence_length=512, mask_length=None,
                  mask_id=103, seed=0, device=0, tokenizer=native.BERT_PROXY_TOKENIZER, chunk=True, min_ids=None,
                  number_labels=9, avg_span_gap=16.0, avg_span_size=2.0, rng_mode=0, mask_policy=0,
-                 mask_per_mille=150, pack=0, span_policy=0, span_noise_per_mille=0, pair=False, fim=None):
+                 mask_per_mille=150, pack=0, span_policy=0, span_noise_per_mille=0, pair=False, fim=None,
+                 best_fit=None):
         L = native.load()
         c = native.default_config(task)
         c.batch_size, c.sequence_length = batch_size, sequence_length
@@ -189,6 +190,8 @@ class DeviceBatcher:
         native.track(self)
         if fim is not None:  # fill-in-the-middle documents (pack=1, clm): right after create
             native.set_fim(self._h, fim)
+        if best_fit is not None:  # best-fit-decreasing rows (pack=1, clm): right after create
+            native.set_best_fit(self._h, best_fit)
 
     def close(self):
         if getattr(self, "_h", None):

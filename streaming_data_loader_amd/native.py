@@ -32,7 +32,7 @@ EXPORTS = [
     "sdl_batcher_push_many", "sdl_batcher_next", "sdl_batcher_flush", "sdl_batch_release",
     "sdl_batcher_push_pair", "sdl_batcher_push_many_pairs", "sdl_process_device_pairs",
     "sdl_batch_position_ids", "sdl_pack_flush_device", "sdl_device_position_ids", "sdl_pack_span_length",
-    "sdl_batch_pair_labels", "sdl_device_pair_labels", "sdl_batcher_set_fim",
+    "sdl_batch_pair_labels", "sdl_device_pair_labels", "sdl_batcher_set_fim", "sdl_batcher_set_best_fit",
     "sdl_process_device", "sdl_process_device_labels", "sdl_json_text_device", "sdl_pickle_frames_device", "sdl_device_to_host", "sdl_set_profiling", "sdl_stage_times",
     "sdl_tokenizer_info_get", "sdl_last_error", "sdl_abi_version", "sdl_json_to_frames",
     "sdl_gzip_inflate_device", "sdl_gzip_inflate_first_device", "sdl_gzip_split_members", "sdl_build_id",
@@ -107,6 +107,11 @@ class Fim(ctypes.Structure):
         ("prefix_id", ctypes.c_int32), ("suffix_id", ctypes.c_int32), ("middle_id", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 3),
     ]
+
+
+class BestFit(ctypes.Structure):
+    """sdl_best_fit: best-fit-decreasing rows of a packed clm handle (sdl_batcher_set_best_fit)."""
+    _fields_ = [("window_records", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
 class JsonText(ctypes.Structure):
@@ -236,6 +241,8 @@ def load(path=LIB_PATH):
     L.sdl_pack_span_length.restype = i64
     L.sdl_batcher_set_fim.argtypes = [vp, ctypes.POINTER(Fim)]
     L.sdl_batcher_set_fim.restype = i64
+    L.sdl_batcher_set_best_fit.argtypes = [vp, ctypes.POINTER(BestFit)]
+    L.sdl_batcher_set_best_fit.restype = i64
     L.sdl_batch_pair_labels.argtypes = [ctypes.POINTER(Batch)]
     L.sdl_batch_pair_labels.restype = ctypes.POINTER(ctypes.c_int32)
     L.sdl_device_pair_labels.argtypes = [vp]
@@ -315,6 +322,14 @@ def set_fim(handle, fim):
         fim = Fim(int(fim.rate_per_mille), int(fim.spm_per_mille), int(fim.prefix_id), int(fim.suffix_id),
                   int(fim.middle_id))
     check(load().sdl_batcher_set_fim(handle, ctypes.byref(fim)))
+
+
+def set_best_fit(handle, best_fit):
+    """sdl_batcher_set_best_fit on a fresh pack = 1 clm handle.  `best_fit`: a native.BestFit, or any
+    object with window_records (batcher.BestFit)."""
+    if not isinstance(best_fit, BestFit):
+        best_fit = BestFit(int(best_fit.window_records))
+    check(load().sdl_batcher_set_best_fit(handle, ctypes.byref(best_fit)))
 
 
 def shard_records(offsets, n_shards):
