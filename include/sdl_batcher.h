@@ -202,6 +202,26 @@ typedef struct sdl_batcher sdl_batcher;
  * sdl_pickle_frames_device frames the four mlm keys over the packed planes, no position_ids key.
  * sdl_batch.token_type_ids is one read-only zero plane shared by the handle's batches.
  *
+ * The same config with a byte-level BPE tokenizer in RoBERTa's form -- a tokenizer.json whose
+ * post_processor is RobertaProcessing (cls / sep name added tokens; trim_offsets and
+ * add_prefix_space only move offsets and are ignored) and which has a <pad> added token -- gives
+ * RoBERTa's pre-training rows.  The contract is the one above with these changes, and only these:
+ * the stream is carry ++ concat over kept r of ([<s>] ++ t_r ++ [</s>]) with the post-processor's
+ * ids, document ends come from the record offsets and never from ids (a text holding the literal
+ * "</s>" is one document, its </s> id a non-candidate inside it); candidates are the filled positions
+ * whose id is none of <s>, </s>, mask_id and <pad> -- id 0 is an ordinary piece ("!") and a
+ * candidate; the random replacement id is uniform below sdl_tokenizer_info.vocab_size; under
+ * mask_policy 2 position j joins the unit before it when j > 0, position j - 1 is a candidate and
+ * the piece of ids[j] neither begins with "Ġ" (the byte-level image of the space: fairseq's
+ * --mask-whole-words rule) nor is an added token, so a document's first id always starts a unit;
+ * the flush row's columns >= c hold input_ids = the <pad> id (not 0), attention_mask 0, labels -100,
+ * position_ids 0.  Rows from *d_rows to the next multiple of B keep the unpacked mlm initial values
+ * (input_ids 0, attention_mask 1), as for WordPiece.  Such a file's eos_id is <|endoftext|> when it
+ * has one, else </s>; under every other config it behaves as the same file with a ByteLevel
+ * post-processor.  A byte-level BPE tokenizer without RobertaProcessing, or without <pad>, is
+ * refused (SDL_ERR_UNSUPPORTED), and so is mask_policy 2 without pack.  roberta-base's own file
+ * marks <mask> with lstrip: clear the flag (pre-training text holds no "<mask>") or the load fails.
+ *
  * Packed span rows (pack = 1 with task span, the Unigram tokenizer, span_policy 1, rng_mode 0):
  * T5's pre-training chunks (t5.data.preprocessors.span_corruption, HF run_t5_mlm_flax.py).  The
  * stream is the clm one with eos = the tokenizer's </s> (record r kept when n_r >= 1 and

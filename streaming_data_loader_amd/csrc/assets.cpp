@@ -415,8 +415,11 @@ static void load_byte_bpe(const JValue &root, const std::string &data_dir, HostT
         (pre->get("use_regex") && !is_true(pre->get("use_regex"))))
         throw std::runtime_error("pre_tokenizer must be ByteLevel(add_prefix_space=false, use_regex=true)");
     const JValue *pp = root.get("post_processor");
-    if (pp && pp->kind != JValue::NUL && !(pp->get("type") && pp->get("type")->is_str("ByteLevel")))
-        throw std::runtime_error("post_processor must be ByteLevel or null (no ids added)");
+    // RobertaProcessing: RoBERTa's form of the file.  The tokenizer still adds no id (the packed mlm
+    // rows frame with its <s> / </s>); trim_offsets / add_prefix_space only move offsets
+    t.roberta_form = pp && pp->get("type") && pp->get("type")->is_str("RobertaProcessing");
+    if (pp && pp->kind != JValue::NUL && !t.roberta_form && !(pp->get("type") && pp->get("type")->is_str("ByteLevel")))
+        throw std::runtime_error("post_processor must be ByteLevel, RobertaProcessing or null (no ids added)");
     t.kind = TOK_BYTE_BPE;
     const JValue *vocab = model->get("vocab");
     if (!vocab || vocab->kind != JValue::OBJ) throw std::runtime_error("model.vocab missing");
@@ -443,9 +446,26 @@ static void load_byte_bpe(const JValue &root, const std::string &data_dir, HostT
         }
     }
     if (t.pieces.size() > 65535) throw std::runtime_error("vocabulary larger than 65535 ids is not supported");
+    if (t.roberta_form) {
+        // post_processor.cls / .sep = [piece, id]: the id of an added token with that content
+        auto framing_id = [&](const char *field) {
+            const JValue *v = pp->get(field);
+            const std::string name = std::string("post_processor.") + field;
+            if (!v || v->kind != JValue::ARR || v->arr.size() != 2 || v->arr[0].kind != JValue::STR ||
+                v->arr[1].kind != JValue::NUM)
+                throw std::runtime_error(name + " must be [piece, id]");
+            for (auto &a : t.added)
+                if (a.second == (int)v->arr[1].num && a.first == v->arr[0].str) return a.second;
+            throw std::runtime_error(name + " is not the id of an added token with that content");
+        };
+        t.cls_id = t.tpl_cls = framing_id("cls");
+        t.sep_id = t.tpl_sep = framing_id("sep");
+        for (auto &a : t.added)
+            if (a.first == "<pad>") t.pad_id = a.second;
+    }
     auto eos = id_of.find("<|endoftext|>");
-    if (eos == id_of.end()) throw std::runtime_error("gpt2 tokenizer lacks <|endoftext|>");
-    t.eos_id = eos->second;
+    if (eos == id_of.end() && !t.roberta_form) throw std::runtime_error("gpt2 tokenizer lacks <|endoftext|>");
+    t.eos_id = eos != id_of.end() ? eos->second : t.sep_id;  // (roberta-base has no <|endoftext|>)
     // byte symbols
     const std::vector<uint32_t> b2c = byte_to_cp();
     std::unordered_map<uint32_t, uint8_t> rev;
@@ -518,6 +538,11 @@ static void load_byte_bpe(const JValue &root, const std::string &data_dir, HostT
     // word table: vocab strings whose own BPE is exactly themselves
     std::vector<bool> is_added(t.pieces.size(), false);
     for (auto &a : t.added) is_added[(size_t)a.second] = true;
+    // the word-start map (fairseq's get_whole_word_mask: the decoded piece starts with a space, whose
+    // byte-level image is "Ġ", U+0120); an added token is a word of its own
+    t.word_start.assign((t.pieces.size() + 31) / 32, 0u);
+    for (size_t id = 0; id < t.pieces.size(); ++id)
+        if (is_added[id] || t.pieces[id].compare(0, 2, "\xC4\xA0") == 0) t.word_start[id >> 5] |= 1u << (id & 31);
     std::vector<VSlot> entries;
     t.vpool.clear();
     t.maxlen_first = t.maxlen_cont = 0;

@@ -54,6 +54,10 @@ struct HostTokenizer {
     std::vector<uint16_t> gpage;           // data/gpt2_classes.bin
     std::vector<uint8_t> gblock;
     size_t word_table_entries = 0;
+    // RoBERTa's form of the file (post_processor RobertaProcessing): cls_id / tpl_cls = <s>, sep_id /
+    // tpl_sep = </s>, pad_id = <pad> (or -1); the tokenizer adds no id itself, the packed mlm rows frame
+    bool roberta_form = false;
+    std::vector<uint32_t> word_start;      // ... bit id set = piece id begins with "Ġ" or is an added token (<= 8 KiB)
 
     // ---- Unigram (t5) ------------------------------------------------------
     std::vector<double> uscore;            // id -> score

@@ -316,6 +316,7 @@ struct sdl_batcher {
     DevBuf<WfSlot> d_first_slots;
     DevBuf<uint32_t> d_cont_bits;  // mask policy 2: the continuation bitmap (HostTokenizer::cont_bits)
     MaskPolicy mpol{};             // sdl_config.mask_policy / mask_per_mille, as k_rows_policy takes them
+    DevBuf<uint32_t> d_word_start;  // byte-level BPE in RoBERTa's form: the word-start map (HostTokenizer::word_start)
     DevBuf<uint16_t> d_gpage, d_byte_id;
     DevBuf<uint8_t> d_gblock;
     DevBuf<MSlot> d_mslots;
@@ -503,6 +504,11 @@ struct sdl_batcher {
     DevBuf<int32_t> o_tt0;                          // packed mlm: the device rows' token_type_ids
     PackMlmParams pack_mlm_params(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off);
     void run_pack_mlm(int64_t R, int64_t rows_cap, int64_t n_chunks, const uint64_t *d_off, hipStream_t st);
+    // ... over a byte-level BPE tokenizer in RoBERTa's form (pack_mlm_bpe.hip): the same carry halves,
+    // row counter and planes, the dense ids in the lists' place
+    bool pack_mlm_bpe() const { return pack_mlm() && tok.kind == TOK_BYTE_BPE; }
+    PackMlmBpeParams pack_mlm_bpe_params(int64_t R, int64_t rows_cap);
+    void run_pack_mlm_bpe(int64_t R, int64_t rows_cap, hipStream_t st);
     // packed span: the chunk length (sdl_pack_span_length); the carry halves hold that many ids each
     int pack_span_N = 0;
     PackSpanParams pack_span_params(int64_t R, int64_t rows_cap);

@@ -521,6 +521,37 @@ hipError_t launch_pack_mlm_rows(const PackMlmParams &q, hipStream_t st);
 // the carry as one last masked row (0 rows when it is empty), rows < B of the planes; the new carry is empty
 hipError_t launch_pack_mlm_flush(const PackMlmParams &q, hipStream_t st);
 
+// pack_mlm_bpe.hip: the same rows over a byte-level BPE tokenizer in RoBERTa's form -- the stream of
+// <s> ids </s> documents read from the dense ids, id 0 an ordinary piece, <pad> behind the flush row,
+// whole words from the word-start map (DESIGN.md §3 "Packed mlm rows"), after launch_records,
+// launch_pack_lengths(.., 2) and the seeded scan into pk_off.  A struct of its own again:
+// k_pack_mlm_rows and the other row kernels compile to what they were.
+struct PackMlmBpeParams {
+    const uint32_t *tok, *rec_tok, *rec_cnt;  // the dense ids and each record's first id / id count
+    const uint32_t *pk_off;                   // [R + 1]: where record r starts in the call's stream; [R] = its length
+    const uint32_t *word_start;               // policy 2: bit i set = piece i starts a word; ceil(vocab_size / 32) words
+    int64_t R, rows_cap;                      // rows_cap * S < 2^32
+    uint64_t seed;                            // the Philox key; a row's masks are those of chunk 0 of record row_cnt + g
+    int32_t S, B, cls, sep;                   // the post-processor's <s> / </s> ids
+    int32_t pad, mask_id, mask_length;        // <pad> (the flush row's tail), <mask>, the row's cap of predictions
+    int32_t policy, per_mille;                // 1 / 2; predictions per 1000 filled positions
+    uint32_t vocab_size;                      // ids, added tokens included: the range of a random replacement
+    const int32_t *carry_ids, *carry_pos;     // the carry the last call left (< S unmasked ids and their position_ids)
+    const uint32_t *carry_len;
+    int32_t *new_ids, *new_pos;               // the other half of the double buffer: this call's carry
+    uint32_t *new_len;
+    const uint64_t *row_cnt;                  // packed rows the handle emitted before this call ...
+    uint64_t *new_row_cnt;                    // ... and after it (the other half, like the carry length)
+    int32_t *ids, *am, *tt, *lab, *pos;       // planes [rows_cap, S]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// the five planes (a wave per packed row: its segment table in LDS, gathered and masked), then the
+// new carry, its length, the row counter and d_rows
+hipError_t launch_pack_mlm_bpe_rows(const PackMlmBpeParams &q, hipStream_t st);
+// the carry as one last masked row with <pad> behind it (0 rows when it is empty), rows < B of the
+// planes; the new carry is empty
+hipError_t launch_pack_mlm_bpe_flush(const PackMlmBpeParams &q, hipStream_t st);
+
 // pack_span.hip: T5 pre-training chunks of N > S ids cut from the stream of ids </s> documents and
 // corrupted by T5's span policy into S-wide rows (sdl_config.pack = 1 under the span task with
 // span_policy 1, DESIGN.md §3 "Packed span rows"), after launch_records, launch_pack_lengths(.., 1)

@@ -1,12 +1,12 @@
 // What the kernels that mask a row under a BERT policy (sdl_config.mask_policy 1 / 2; DESIGN.md §3
 // "Masking policies") share as code: the Philox RNG contract, the k-smallest select, the wave as
 // mlm_pick.hpp asks for it, the row's budget and the 80/10/10 thresholds.  The kernels are the
-// unpaired rows (rows_device.hpp row_policy_one), the NSP / SOP pair rows (pair_mlm.hip) and the
-// packed rows (pack_mlm.hip).
+// unpaired rows (rows_device.hpp row_policy_one), the NSP / SOP pair rows (pair_mlm.hip), the
+// packed rows (pack_mlm.hip) and the packed rows over byte-level BPE (pack_mlm_bpe.hip).
 //
 // The candidates, the pick (keys, policy-1 select, whole-word unit build) and the replacement draws
-// are NOT here: they stand in each of the three callers, copied, and a change to one is made to all
-// three.  Moved into force-inlined helpers (any one of them alone, with value, reference or scalar
+// are NOT here: they stand in each of the four callers, copied, and a change to one is made to all
+// four.  Moved into force-inlined helpers (any one of them alone, with value, reference or scalar
 // parameters) they compile to other instruction streams than the copies do, the unpaired and the
 // packed rows stages measured 1-3 % slower and a flush kernel gained scratch (DESIGN.md §4 "One
 // policy text").  What is here compiles to the callers' code as it was, instruction for instruction.

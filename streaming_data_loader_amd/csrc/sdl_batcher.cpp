@@ -219,6 +219,57 @@ void sdl_batcher::run_pack_mlm(int64_t R, int64_t rows_cap, int64_t n_chunks, co
     pk_cur ^= 1;
     pk_ran = true;
 }
+// packed mlm over byte-level BPE in RoBERTa's form: packed mlm's carry halves, row counter and planes,
+// the dense ids, the post-processor's <s> / </s>, <pad> and the word-start map
+PackMlmBpeParams sdl_batcher::pack_mlm_bpe_params(int64_t R, int64_t rows_cap) {
+    const PackParams c = pack_params(R, rows_cap);
+    uint64_t *cnt = reinterpret_cast<uint64_t *>(pk_meta.p + 4);
+    PackMlmBpeParams q{};
+    q.tok = c.tok;
+    q.rec_tok = c.rec_tok;
+    q.rec_cnt = c.rec_cnt;
+    q.pk_off = c.pk_off;
+    q.word_start = d_word_start.p;
+    q.R = R;
+    q.rows_cap = rows_cap;
+    q.seed = P.seed;
+    q.S = P.S;
+    q.B = P.B;
+    q.cls = tok.tpl_cls;
+    q.sep = tok.tpl_sep;
+    q.pad = tok.pad_id;
+    q.mask_id = P.mask_id;
+    q.mask_length = P.mask_length;
+    q.policy = mpol.policy;
+    q.per_mille = mpol.per_mille;
+    q.vocab_size = mpol.vocab_size;
+    q.carry_ids = c.carry_ids;
+    q.carry_pos = c.carry_pos;
+    q.carry_len = c.carry_len;
+    q.new_ids = c.new_ids;
+    q.new_pos = c.new_pos;
+    q.new_len = c.new_len;
+    q.row_cnt = cnt + pk_cur;
+    q.new_row_cnt = cnt + (pk_cur ^ 1);
+    q.ids = o_ids.p;
+    q.am = o_am.p;
+    q.tt = o_tt0.p;
+    q.lab = o_lab.p;
+    q.pos = o_tt.p;
+    q.d_rows = pk_meta.p;
+    return q;
+}
+// the call's rows from rec_tok / rec_cnt and the dense ids (after launch_records): packed lengths
+// with <s> and </s>, their scan seeded with the carry length, the masked rows and the new carry
+// -- no host synchronisation
+void sdl_batcher::run_pack_mlm_bpe(int64_t R, int64_t rows_cap, hipStream_t st) {
+    pk_off.ensure((size_t)R + 1);
+    HIP_TRY(launch_pack_lengths(pack_params(R, rows_cap), st, 2));
+    HIP_TRY(launch_exclusive_scan(rec_rows.p, pk_off.p, R, scan_tmp.p, st, pk_off.p));
+    HIP_TRY(launch_pack_mlm_bpe_rows(pack_mlm_bpe_params(R, rows_cap), st));
+    pk_cur ^= 1;
+    pk_ran = true;
+}
 // packed span: carry halves of NP ids (no position_ids), the row counter beside the carry lengths as
 // packed mlm keeps it, the dense Unigram ids, three planes with S / 4 labels a row
 PackSpanParams sdl_batcher::pack_span_params(int64_t R, int64_t rows_cap) {
@@ -288,7 +339,8 @@ void sdl_batcher::run_pack_flush(hipStream_t st) {
     o_lab.ensure(plane);
     if (pack_mlm()) {
         o_tt0.ensure(plane);
-        HIP_TRY(launch_pack_mlm_flush(pack_mlm_params(0, rows_cap, 0, nullptr), st));
+        if (pack_mlm_bpe()) HIP_TRY(launch_pack_mlm_bpe_flush(pack_mlm_bpe_params(0, rows_cap), st));
+        else HIP_TRY(launch_pack_mlm_flush(pack_mlm_params(0, rows_cap, 0, nullptr), st));
     } else {
         HIP_TRY(launch_pack_flush(pack_params(0, rows_cap), st));
     }
@@ -554,7 +606,8 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
         if (!piped) mark(5);
         if (pack()) {  // rec_tok / rec_cnt exist: the stream's rows instead of row scan, row map and k_rows
             mark(6);
-            if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
+            if (pack_mlm_bpe()) run_pack_mlm_bpe(R, rows_cap, s);  // (byte-level BPE: from the dense ids)
+            else if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
             else if (pack_span()) run_pack_span(R, rows_cap, s);
             else if (fim_on) run_pack_fim(R, rows_cap, first_record, s);
             else if (bf_on) run_pack_best_fit(R, rows_cap, s);
@@ -1168,6 +1221,7 @@ void upload_tables(sdl_batcher *h) {
         d.mslots = h->d_mslots.upload(t.mslots);
         d.byte_id = h->d_byte_id.upload(t.byte_id.data(), 256);
         d.mslot_mask = t.mslot_mask;
+        if (t.roberta_form) h->d_word_start.upload(t.word_start);  // (no kernel argument but pack_mlm_bpe.hip's)
     }
     if (t.kind == TOK_UNIGRAM) {
         d.uscore = h->d_uscore.upload(t.uscore);
@@ -1454,12 +1508,20 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
                         "pair = 2..4 with a byte-level BPE or Unigram tokenizer: mlm sentence pairs need a WordPiece "
                         "tokenizer with [CLS] and [SEP] ids");
         // (and packed mlm rows, for the same reason)
-        if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM &&
+        // (... over byte-level BPE in RoBERTa's form: <s> / </s> from its post-processor, <pad> behind the flush row)
+        const bool roberta = h->tok.kind == TOK_BYTE_BPE && h->tok.roberta_form;
+        if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM && roberta && h->tok.pad_id < 0)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pack = 1 under the MLM task with a byte-level BPE tokenizer needs a <pad> added token: the "
+                        "flush row's tail holds its id");
+        if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM && !roberta &&
             (h->tok.kind != TOK_WORDPIECE || h->tok.tpl_cls < 0 || h->tok.tpl_sep < 0))
             return fail(SDL_ERR_UNSUPPORTED,
-                        "pack = 1 under the MLM task needs a WordPiece tokenizer with [CLS] and [SEP] ids: packed mlm "
-                        "rows are not built for byte-level BPE or Unigram tokenizers");
-        if (cfg->mask_policy == SDL_MASK_BERT_WHOLE_WORD && h->tok.kind != TOK_WORDPIECE)
+                        "pack = 1 under the MLM task needs a WordPiece tokenizer with [CLS] and [SEP] ids, or a "
+                        "byte-level BPE tokenizer in RoBERTa's form (post_processor RobertaProcessing, a <pad> token): "
+                        "packed mlm rows are not built for other byte-level BPE tokenizers or Unigram");
+        if (cfg->mask_policy == SDL_MASK_BERT_WHOLE_WORD && h->tok.kind != TOK_WORDPIECE &&
+            !(roberta && cfg->pack == 1 && cfg->task == SDL_TASK_MLM))
             return fail(SDL_ERR_UNSUPPORTED,
                         "mask_policy 2 (SDL_MASK_BERT_WHOLE_WORD) needs a WordPiece tokenizer: whole words are "
                         "not defined for byte-level BPE or Unigram pieces");
