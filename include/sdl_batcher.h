@@ -33,9 +33,9 @@ extern "C" {
 #endif
 
 /* 9 still: sdl_zstd_split_frames, sdl_zstd_inflate_device, the three sentence-pair calls, the
- * two pair-label accessors, sdl_pack_span_length, sdl_batcher_set_fim and sdl_batcher_set_best_fit
- * (with sdl_best_fit) were added without changing any existing call or struct (an additive change
- * keeps the version). */
+ * two pair-label accessors, sdl_pack_span_length, sdl_batcher_set_fim, sdl_batcher_set_best_fit
+ * (with sdl_best_fit) and sdl_config.pair = 6 were added without changing any
+ * existing call or struct (an additive change keeps the version). */
 #define SDL_ABI_VERSION 9
 
 enum {
@@ -106,8 +106,10 @@ struct sdl_config {
             int32_t pair;                 /* SDL_PAIR_*, WordPiece: 0 = one text per record; 1 = two texts per
                                              example in one [CLS] A [SEP] B [SEP] row (single-class /
                                              multi-label); 2..4 = that row under mlm with a BERT masking
-                                             policy and a pair label ("Sentence pairs" below).  Other
-                                             values are refused */
+                                             policy and a pair label ("Sentence pairs" below); 6 = byte-level
+                                             BPE, packed clm: a prompt and a completion per example with
+                                             completion-only labels ("Packed rows" below).  Other values, 5
+                                             among them, are refused */
         };
     };
 };
@@ -241,7 +243,38 @@ typedef struct sdl_batcher sdl_batcher;
  * span_policy 0 and a chunk with t(N) + m(N) + 1 > S/4, m(N) + 1 > 100 or N > 3584 (SDL_ERR_ARG;
  * this replaces policy 1's full-row rule), a tokenizer that is not Unigram (SDL_ERR_UNSUPPORTED);
  * sdl_multi_create and sdl_json_to_frames return SDL_ERR_UNSUPPORTED; sdl_pickle_frames_device
- * frames the three span keys over the packed planes.  The host path is the clm one above. */
+ * frames the three span keys over the packed planes.  The host path is the clm one above.
+ *
+ * Prompt / completion examples (pair = 6, SDL_PAIR_CLM_COMPLETION; accepted only with task clm,
+ * pack = 1 and a byte-level BPE tokenizer that plain packed clm accepts, 3 <= S <= 4096): what
+ * supervised fine-tuning packs (TRL's completion_only_loss with packing, the OpenAI and Alpaca
+ * recipes).  A pair call carries n_pairs examples: text range 2e is the prompt A_e and range
+ * 2e + 1 the completion B_e.  The tokenizer runs once over the 2 n_pairs ranges, each a record of
+ * its own: A and B are tokenized separately, a pre-token never spans the seam, and the caller puts
+ * the leading space into B.  With a_e, b_e the two id lists (nA, nB ids), example e is kept when
+ * nB >= 1 and nA + nB + 1 >= min_ids -- an empty prompt is legal, an example without a completion
+ * id trains nothing and is dropped -- and a kept example's document is a_e ++ b_e ++ [eos].  The
+ * stream is carry ++ concat of the kept documents, cut into full rows exactly as above:
+ * input_ids, attention_mask, position_ids (running on across the A/B seam, restarting only at a
+ * row start and after a document's eos), the row count, the padding rows and the carry rule are
+ * those of plain packed rows over these documents.  labels is -100 at every position that holds
+ * an id of some a_e and the id elsewhere, on b_e and on the eos.  A row that lies wholly inside a
+ * long prompt is all -100 and is still emitted.  The carry keeps, beside its ids and positions,
+ * which of its positions are prompt positions: a call that ends inside a prompt continues
+ * correctly, and the flush row's labels are -100 there as well as behind the carry.
+ * d_record_rows has n_pairs entries, nA + nB + 1 or 0 when the example is dropped; d_tokens counts
+ * the ids of both sides; rows_capacity = (ids + n_pairs + S - 1) / S + 1 rounded up to B; seed
+ * and first_record are unused and the label arguments of the pair calls are ignored.
+ * sdl_process_device_pairs, sdl_batcher_push_pair and sdl_batcher_push_many_pairs serve such a
+ * handle; sdl_pack_flush_device, sdl_device_position_ids, sdl_batcher_next and sdl_batcher_flush
+ * work as on a packed handle (every full batch a call completes is queued in order, the flush row
+ * comes last, a one-pair push goes through the bulk path); the unpaired calls return
+ * SDL_ERR_STATE; sdl_pickle_frames_device frames the three reference keys over these planes.
+ * sdl_batcher_create refuses pair = 6 with pack = 0, another task or a WordPiece / Unigram
+ * tokenizer (SDL_ERR_UNSUPPORTED) and S < 3 (SDL_ERR_ARG); sdl_batcher_set_fim and
+ * sdl_batcher_set_best_fit return SDL_ERR_STATE on such a handle; sdl_multi_create and
+ * sdl_json_to_frames return SDL_ERR_UNSUPPORTED.  The value is 6, not 5: 5 stays refused
+ * (SDL_ERR_ARG) like every other value outside 0..4 and 6. */
 
 /* ---- Sentence pairs (sdl_config.pair = 1; tasks single-class and multi-label, WordPiece) ----
  * No counterpart in the reference (SimpleData.alt_text is tokenized and dropped, dataset.rs:47):
@@ -300,7 +333,8 @@ enum {
     SDL_PAIR_ROWS = 1,    /* single-class / multi-label: [CLS] A [SEP] B [SEP] rows */
     SDL_PAIR_MLM = 2,     /* mlm: pairs as given, pair label 0 everywhere */
     SDL_PAIR_MLM_NSP = 3, /* mlm: next-sentence draws */
-    SDL_PAIR_MLM_SOP = 4  /* mlm: sentence-order draws */
+    SDL_PAIR_MLM_SOP = 4, /* mlm: sentence-order draws */
+    SDL_PAIR_CLM_COMPLETION = 6 /* packed clm: prompt / completion examples, labels -100 on the prompt */
 };
 
 /* Defaults of the reference masking cases (masking_cases.rs:38-94) for `task`:

@@ -77,6 +77,10 @@ class Gpt:
     fim: Optional[Fim] = None
     # pack only, not with fim: best-fit-decreasing rows (sdl_batcher_set_best_fit, applied right after create)
     best_fit: Optional[BestFit] = None
+    # pack only, not with fim or best_fit: sdl_config.pair = 6 (DESIGN.md §3 "Prompt / completion
+    # rows") -- an example is a (prompt, completion) pair given to create_sync_batch_pair /
+    # create_sync_batches_pairs, one document of the stream, labels -100 on the prompt's ids
+    completion_only: bool = False
 
 
 @dataclass
@@ -249,6 +253,8 @@ def _native_config(batch_config, dataset_config, chunk, seed, device, first_reco
         c.pair = int(dataset_config.pair)
     if isinstance(dataset_config, (Gpt, Mask, Span)):
         c.pack = 1 if dataset_config.pack else 0
+    if isinstance(dataset_config, Gpt) and dataset_config.completion_only:
+        c.pair = native.SDL_PAIR_CLM_COMPLETION
     if isinstance(dataset_config, Span):
         c.avg_span_gap, c.avg_span_size = dataset_config.avg_span_gap, dataset_config.avg_span_size
         c.span_policy, c.span_noise_per_mille = dataset_config.policy, dataset_config.noise_per_mille
@@ -372,7 +378,7 @@ class _NativeBatcher(Batcher):
         self.batch_config = batch_config
         self.dataset_config = dataset_config
         # mlm sentence pairs: the key DataSet.to_dict() files the pair labels under (the frames' fifth key)
-        self.pair_key = None if c.pair < native.SDL_PAIR_MLM else \
+        self.pair_key = None if not native.SDL_PAIR_MLM <= c.pair <= native.SDL_PAIR_MLM_SOP else \
             "sentence_order_label" if c.pair == native.SDL_PAIR_MLM_SOP else "next_sentence_label"
 
     @classmethod
@@ -453,7 +459,8 @@ class GenTokenizer(_NativeBatcher):
 
     def create_sync_batch_pair(self, a, b) -> Optional[DataSet]:
         """MLM sentence pairs (Mask(pair=2 or 4)): one example of two texts, sdl_batcher_push_pair.
-        Next-sentence draws (pair=3) need a call of several pairs: create_sync_batches_pairs."""
+        Next-sentence draws (pair=3) need a call of several pairs: create_sync_batches_pairs.
+        Gpt(pack=True, completion_only=True): one (prompt, completion) example."""
         def raw(t):
             return t.encode("utf-8") if isinstance(t, str) else bytes(t)
         return self._push_pair(raw(a), raw(b))
@@ -461,7 +468,9 @@ class GenTokenizer(_NativeBatcher):
     def create_sync_batches_pairs(self, pairs):
         """MLM sentence pairs (Mask(pair=2..4)): (A, B) examples in one device pass -- one call for the
         next-sentence draw, which picks a foreign B among this call's pairs; returns the batches
-        emitted, in order, their pair labels in DataSet.pair_labels."""
+        emitted, in order, their pair labels in DataSet.pair_labels.
+        Gpt(pack=True, completion_only=True): (prompt, completion) examples, packed rows whose labels
+        are -100 on the prompt ids."""
         from .device import arena_from_pairs
         arena, offs = arena_from_pairs(pairs)
         return self.push_arena(arena, offs, pairs=True)

@@ -21,7 +21,7 @@ BUILD = os.path.join(REPO, "build", "sdl")
 LIB = os.path.join(PKG, "libsdl_batcher.so")
 ARCH = os.environ.get("SDL_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pack_fim.hip", "pack_bestfit.hip", "pack_mlm.hip", "pack_mlm_bpe.hip", "pack_span.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
+SOURCES = ["tokenize_wordpiece.hip", "tokenize_bpe.hip", "tokenize_unigram.hip", "pipeline.hip", "pack.hip", "pack_fim.hip", "pack_bestfit.hip", "pack_prompt.hip", "pack_mlm.hip", "pack_mlm_bpe.hip", "pack_span.hip", "pair.hip", "pair_mlm.hip", "json_text.hip", "transport_frame.hip", "inflate.hip", "zstd.hip",
            "assets.cpp", "sdl_batcher.cpp", "provider_json.cpp", "provider_gzip.cpp", "provider_zstd.cpp", "transport.cpp"]
 HEADERS = ["common.hpp", "device_util.hpp", "kernels.hpp", "tok_device.hpp", "assets.hpp", "json.hpp", "unigram.hpp", "handle.hpp",
            "rows_device.hpp", "list_index.hpp", "mlm_pick.hpp", "mlm_policy_device.hpp", "span_noise.hpp", "pair_draw.hpp", "pack_queue.hpp", "pack_search.hpp", "wp_pack.hpp", "wp_extent.hpp", "wp_first.hpp", "zstd_format.hpp"]
@@ -31,7 +31,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # (the older sources keep the flags, and so the machine code, they had)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"pack_mlm.hip": NO_PACKED_FP32, "pack_span.hip": NO_PACKED_FP32, "pack_fim.hip": NO_PACKED_FP32,
-               "pack_bestfit.hip": NO_PACKED_FP32, "pack_mlm_bpe.hip": NO_PACKED_FP32}
+               "pack_bestfit.hip": NO_PACKED_FP32, "pack_mlm_bpe.hip": NO_PACKED_FP32, "pack_prompt.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

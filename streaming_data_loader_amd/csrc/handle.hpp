@@ -477,10 +477,16 @@ struct sdl_batcher {
     // S-wide rows; ids only -- no position_ids plane, so the batches have no fourth plane
     bool pack_span() const { return pack() && P.task == SDL_TASK_SPAN; }
     bool plane4() const { return with_tt() || (pack() && !pack_span()); }
-    // sdl_config.pair != 0: a call's 2 n text ranges are n examples of two texts, one row each
+    // sdl_config.pair 1..4: a call's 2 n text ranges are n examples of two texts, one row each
     // (pair = 1: pair.hip, the label tasks; pair 2..4: pair_mlm.hip, mlm with a drawn pair label)
-    bool pair() const { return cfg.pair != 0; }
-    bool pair_mlm() const { return cfg.pair >= SDL_PAIR_MLM; }
+    bool pair() const { return cfg.pair != 0 && !pair_clm(); }
+    bool pair_mlm() const { return cfg.pair >= SDL_PAIR_MLM && cfg.pair <= SDL_PAIR_MLM_SOP; }
+    // sdl_config.pair = 6 (pack = 1, clm; pack_prompt.hip): the 2 n text ranges are n prompt /
+    // completion examples, each one document of the packed stream -- the packed sequence over 2 n
+    // records, none of the row-per-pair branches
+    bool pair_clm() const { return cfg.pair == SDL_PAIR_CLM_COMPLETION; }
+    // the pair entry points serve the handle (and the unpaired ones refuse it)
+    bool pair_calls() const { return cfg.pair != 0; }
 
     std::shared_ptr<BatchPool> pool;
     HostBatch *new_batch() {
@@ -540,6 +546,11 @@ struct sdl_batcher {
     DevBuf<uint32_t> bf_foff, bf_run, bf_win;
     DevBuf<uint4> bf_piece;
     void run_pack_best_fit(int64_t R, int64_t rows_cap, hipStream_t st);
+    // pair = 6 (pack_prompt.hip): the carry's prompt flags, double buffered beside pk_carry (S words a
+    // half; carry_pos stays what k_pack_flush's callers read)
+    DevBuf<uint32_t> pk_pflag;
+    PackPromptParams pack_prompt_params(int64_t E, int64_t rows_cap);
+    void run_pack_prompt(int64_t R, int64_t rows_cap, hipStream_t st);
     DevBuf<uint32_t> pair_rb;  // pair != 0: the one segment's record bounds {0, n_pairs}
     DevBuf<int32_t> o_pair_lab;  // pair 2..4: the pair label of every row of the last call, grown with the row planes
     bool pair_lab_ran = false;   // ... written by a call (sdl_device_pair_labels is NULL before)

@@ -466,6 +466,32 @@ hipError_t launch_fim_plan(const PackFimParams &q, hipStream_t st);
 // carry, its length, the record counter and d_rows
 hipError_t launch_pack_fim_rows(const PackFimParams &q, hipStream_t st);
 
+// pack_prompt.hip: pack.hip's rows over prompt / completion examples (sdl_config.pair = 6, DESIGN.md
+// §3 "Prompt / completion rows"): text ranges 2e and 2e + 1 of a call are one document a_e ++ b_e ++
+// [eos], and labels is -100 on the ids of a_e.  A struct and kernels of their own again: pack.hip,
+// pack_fim.hip and pack_bestfit.hip compile to what they were.
+struct PackPromptParams {
+    const uint32_t *tok, *rec_tok, *rec_cnt;  // the dense ids and each range's first id / id count, [2 E]
+    uint32_t *rec_len;                        // out [E]: stream positions example e adds (nA + nB + 1, 0 = dropped)
+    uint32_t *pk_off;                         // [E + 1]: where example e starts in the call's stream; [E] = its length
+    int64_t E, rows_cap;                      // E = n_pairs; rows_cap * S < 2^32
+    int32_t S, B, eos, min_ids;
+    const int32_t *carry_ids, *carry_pos;     // the carry the last call left (< S ids and their position_ids)
+    const uint32_t *carry_flag;               // ... and 1 where the carry's id is a prompt id (labels -100)
+    const uint32_t *carry_len;
+    int32_t *new_ids, *new_pos;               // the other half of the double buffer: this call's carry
+    uint32_t *new_flag, *new_len;
+    int32_t *ids, *am, *lab, *pos;            // planes [rows_cap, S]
+    uint32_t *d_rows;                         // out: rows emitted
+};
+// rec_len and pk_off[0] = the carry length: then launch_exclusive_scan(rec_len, pk_off, E, tmp, st, pk_off)
+hipError_t launch_prompt_lengths(const PackPromptParams &q, hipStream_t st);
+// the four planes (the gather over the flat output index), then the new carry with its flags, its
+// length and d_rows
+hipError_t launch_prompt_rows(const PackPromptParams &q, hipStream_t st);
+// the carry as one last row (0 rows when it is empty), rows < B of the planes; the new carry is empty
+hipError_t launch_prompt_flush(const PackPromptParams &q, hipStream_t st);
+
 // pack_bestfit.hip: packed CLM rows by best-fit-decreasing (sdl_batcher_set_best_fit, DESIGN.md §3
 // "Best-fit rows"): documents longer than a row are cut into row-sized pieces, every other document
 // and every leftover tail stays whole, and the tails of a window of W records are placed into rows

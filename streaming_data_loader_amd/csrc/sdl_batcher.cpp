@@ -127,6 +127,51 @@ void sdl_batcher::run_pack_fim(int64_t R, int64_t rows_cap, uint64_t first_recor
     pk_cur ^= 1;
     pk_ran = true;
 }
+// prompt / completion examples (pair = 6): packed clm's carry halves with a half of prompt flags
+// each, E examples over the 2 E ranges' rec_tok / rec_cnt
+PackPromptParams sdl_batcher::pack_prompt_params(int64_t E, int64_t rows_cap) {
+    const PackParams c = pack_params(2 * E, rows_cap);
+    pk_pflag.ensure(2 * (size_t)P.S);
+    PackPromptParams q{};
+    q.tok = c.tok;
+    q.rec_tok = c.rec_tok;
+    q.rec_cnt = c.rec_cnt;
+    q.rec_len = c.rec_len;
+    q.pk_off = c.pk_off;
+    q.E = E;
+    q.rows_cap = rows_cap;
+    q.S = c.S;
+    q.B = c.B;
+    q.eos = c.eos;
+    q.min_ids = c.min_ids;
+    q.carry_ids = c.carry_ids;
+    q.carry_pos = c.carry_pos;
+    q.carry_flag = pk_pflag.p + (size_t)pk_cur * (size_t)P.S;
+    q.carry_len = c.carry_len;
+    q.new_ids = c.new_ids;
+    q.new_pos = c.new_pos;
+    q.new_flag = pk_pflag.p + (size_t)(pk_cur ^ 1) * (size_t)P.S;
+    q.new_len = c.new_len;
+    q.ids = c.ids;
+    q.am = c.am;
+    q.lab = c.lab;
+    q.pos = c.pos;
+    q.d_rows = c.d_rows;
+    return q;
+}
+// the call's rows from rec_tok / rec_cnt of its R = 2 E text ranges (after launch_records): the
+// examples' packed lengths, their scan seeded with the carry length, the gather and the new carry
+// with its prompt flags -- no host synchronisation
+void sdl_batcher::run_pack_prompt(int64_t R, int64_t rows_cap, hipStream_t st) {
+    const int64_t E = R / 2;
+    pk_off.ensure((size_t)E + 1);
+    const PackPromptParams q = pack_prompt_params(E, rows_cap);
+    HIP_TRY(launch_prompt_lengths(q, st));
+    HIP_TRY(launch_exclusive_scan(rec_rows.p, pk_off.p, E, scan_tmp.p, st, pk_off.p));
+    HIP_TRY(launch_prompt_rows(q, st));
+    pk_cur ^= 1;
+    pk_ran = true;
+}
 // best-fit rows (sdl_batcher_set_best_fit): the plan kernel (a wave a window), the scan of the windows'
 // row counts, the row kernel -- launches only, no host synchronisation; the carry stays empty
 void sdl_batcher::run_pack_best_fit(int64_t R, int64_t rows_cap, hipStream_t st) {
@@ -341,6 +386,8 @@ void sdl_batcher::run_pack_flush(hipStream_t st) {
         o_tt0.ensure(plane);
         if (pack_mlm_bpe()) HIP_TRY(launch_pack_mlm_bpe_flush(pack_mlm_bpe_params(0, rows_cap), st));
         else HIP_TRY(launch_pack_mlm_flush(pack_mlm_params(0, rows_cap, 0, nullptr), st));
+    } else if (pair_clm()) {
+        HIP_TRY(launch_prompt_flush(pack_prompt_params(0, rows_cap), st));
     } else {
         HIP_TRY(launch_pack_flush(pack_params(0, rows_cap), st));
     }
@@ -425,6 +472,7 @@ int64_t sdl_batcher::rows_capacity(int64_t N, int64_t R) const {
     int64_t cap = P.chunk ? (ids + R * (F + P.S - 1)) / P.S + 1 : R;
     if (pack()) cap = (ids + R + P.S - 1) / P.S + 1;  // the carry (< S) + every id + an eos per record
     if (fim_on) cap = (ids + 4 * R + P.S - 1) / P.S + 1;  // ... + three sentinels per record (fill-in-the-middle)
+    if (pair_clm()) cap = (ids + R / 2 + P.S - 1) / P.S + 1;  // ... an eos per example of two ranges (pair = 6)
     // best fit: the full rows hold S ids each.  Of a window's open rows at most one is at most half
     // full -- the tail that opened the later of two such rows (<= S / 2 ids, as the row never holds
     // fewer) would have fitted the earlier one, whose room was >= S / 2 then as now -- so a window
@@ -609,6 +657,7 @@ void sdl_batcher::run_device(const uint8_t *d_text, int64_t N, const uint64_t *d
             if (pack_mlm_bpe()) run_pack_mlm_bpe(R, rows_cap, s);  // (byte-level BPE: from the dense ids)
             else if (pack_mlm()) run_pack_mlm(R, rows_cap, n_chunks, d_off, s);  // (from the lists: no dense ids)
             else if (pack_span()) run_pack_span(R, rows_cap, s);
+            else if (pair_clm()) run_pack_prompt(R, rows_cap, s);
             else if (fim_on) run_pack_fim(R, rows_cap, first_record, s);
             else if (bf_on) run_pack_best_fit(R, rows_cap, s);
             else run_pack(R, rows_cap, s);
@@ -798,7 +847,8 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
                                const uint64_t *label_off) {
     const int64_t N = (int64_t)offsets[R];
     // pair = 1: R text ranges are E = R / 2 examples -- one label set, one row, one cadence step each
-    const int64_t E = pair() ? R / 2 : R;
+    // (pair = 6: one document of the packed stream each)
+    const int64_t E = pair_calls() ? R / 2 : R;
     // one pinned staging blob, one H2D: text | offsets | labels | label offsets
     const bool with_labels = simple() && labels && label_off;  // validated by the caller
     const uint64_t L = with_labels ? label_off[E] - label_off[0] : 0;
@@ -886,7 +936,7 @@ void sdl_batcher::process_host(const uint8_t *arena, const uint64_t *offsets, in
         queue_packed_rows();
         hc.lap("h2d+kernels+d2h");
         hc.report(N, 0, pool ? pool->fresh : 0);
-        n_records += (uint64_t)R;
+        n_records += (uint64_t)E;
         return;
     }
     if (direct) {
@@ -1086,9 +1136,17 @@ int check_config(const sdl_config *cfg) {
         cfg->task != SDL_TASK_SPAN && cfg->task != SDL_TASK_SINGLE_CLASS)
         return fail(SDL_ERR_UNSUPPORTED, "unknown task");
     // (sentence pairs first: a task or tokenizer they are not built for is named as that)
-    if (cfg->pair < SDL_PAIR_NONE || cfg->pair > SDL_PAIR_MLM_SOP)
-        return fail(SDL_ERR_ARG, "pair must be 0 (one text per record), 1 (sentence pairs) or 2..4 (mlm sentence pairs); "
-                                 "other values are reserved");
+    if (cfg->pair < SDL_PAIR_NONE || (cfg->pair > SDL_PAIR_MLM_SOP && cfg->pair != SDL_PAIR_CLM_COMPLETION))
+        return fail(SDL_ERR_ARG, "pair must be 0 (one text per record), 1 (sentence pairs), 2..4 (mlm sentence pairs) or "
+                                 "6 (packed clm prompt / completion examples); other values are reserved");
+    if (cfg->pair == SDL_PAIR_CLM_COMPLETION) {
+        if (cfg->task != SDL_TASK_CLM || cfg->pack != 1)
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pair = 6 (prompt / completion examples with completion-only labels) is built for packed clm "
+                        "rows only: task clm with pack = 1");
+        if (cfg->sequence_length < 3)
+            return fail(SDL_ERR_ARG, "pair = 6 needs 3 <= sequence_length <= 4096");
+    }
     // (packed mlm rows next, so that each of their refusals names pack)
     if (cfg->pack == 1 && cfg->task == SDL_TASK_MLM) {
         if (cfg->mask_policy == SDL_MASK_REFERENCE)
@@ -1100,7 +1158,7 @@ int check_config(const sdl_config *cfg) {
         if (cfg->rng_mode == 1)
             return fail(SDL_ERR_UNSUPPORTED, "pack = 1 under the MLM task needs rng_mode 0: the masks are on the Philox contract");
     }
-    if (cfg->pair >= SDL_PAIR_MLM) {
+    if (cfg->pair >= SDL_PAIR_MLM && cfg->pair <= SDL_PAIR_MLM_SOP) {
         if (cfg->task != SDL_TASK_MLM)
             return fail(SDL_ERR_ARG, "pair = 2..4 (mlm sentence pairs, NSP / SOP draws) apply to the MLM task only");
         if (cfg->mask_policy == SDL_MASK_REFERENCE)
@@ -1336,7 +1394,7 @@ void fill_row_params(sdl_batcher *h) {
         P.chunk = 0;
         P.min_ids = 0;
     }
-    if (cfg->pair >= SDL_PAIR_MLM) {  // mlm sentence pairs: one row per pair, `chunk` and `min_ids` ignored
+    if (cfg->pair >= SDL_PAIR_MLM && cfg->pair <= SDL_PAIR_MLM_SOP) {  // mlm sentence pairs: one row per pair, `chunk` and `min_ids` ignored
         P.chunk = 0;
         P.min_ids = 0;
     }
@@ -1503,7 +1561,11 @@ int sdl_batcher_create(const sdl_config *cfg, const char *tokenizer_path, const 
             if (int rc = pack_span_length(cfg, &h->pack_span_N)) return rc;
         }
         // (mlm sentence pairs first, so that the refusal names them also under mask_policy 2)
-        if (cfg->pair >= SDL_PAIR_MLM && (h->tok.kind != TOK_WORDPIECE || h->tok.cls_id < 0 || h->tok.sep_id < 0))
+        if (cfg->pair == SDL_PAIR_CLM_COMPLETION && (h->tok.kind != TOK_BYTE_BPE || h->tok.eos_id < 0))
+            return fail(SDL_ERR_UNSUPPORTED,
+                        "pair = 6 with a WordPiece or Unigram tokenizer: prompt / completion examples need the byte-level "
+                        "BPE tokenizer with an <|endoftext|> id that pack = 1 under the CLM task needs");
+        if (cfg->pair >= SDL_PAIR_MLM && cfg->pair <= SDL_PAIR_MLM_SOP && (h->tok.kind != TOK_WORDPIECE || h->tok.cls_id < 0 || h->tok.sep_id < 0))
             return fail(SDL_ERR_UNSUPPORTED,
                         "pair = 2..4 with a byte-level BPE or Unigram tokenizer: mlm sentence pairs need a WordPiece "
                         "tokenizer with [CLS] and [SEP] ids");
@@ -1563,7 +1625,7 @@ void sdl_batcher_destroy(sdl_batcher *h) { delete h; }
 int sdl_batcher_push(sdl_batcher *h, const uint8_t *utf8, size_t len, const uint32_t *labels, size_t n_labels,
                      sdl_batch *out) {
     if (!h || (!utf8 && len) || (!labels && n_labels)) return fail(SDL_ERR_ARG, "null argument");
-    if (h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push on a handle created with pair = 1: use sdl_batcher_push_pair");
+    if (h->pair_calls()) return fail(SDL_ERR_STATE, "sdl_batcher_push on a handle created with pair = 1: use sdl_batcher_push_pair");
     if (h->multi()) {
         if (int rc = check_labels(h, labels, n_labels)) return rc;
     }
@@ -1596,7 +1658,7 @@ int sdl_batcher_push(sdl_batcher *h, const uint8_t *utf8, size_t len, const uint
 int sdl_batcher_push_many(sdl_batcher *h, const uint8_t *arena, const uint64_t *offsets, size_t n_records,
                           const uint32_t *labels, const uint64_t *label_offsets, size_t *n_emitted) {
     if (!h || !offsets || (!arena && n_records && offsets[n_records])) return fail(SDL_ERR_ARG, "null argument");
-    if (h->pair())
+    if (h->pair_calls())
         return fail(SDL_ERR_STATE, "sdl_batcher_push_many on a handle created with pair = 1: use sdl_batcher_push_many_pairs");
     return push_many_checked(h, arena, offsets, n_records, n_records, labels, label_offsets, n_emitted);
 }
@@ -1604,7 +1666,7 @@ int sdl_batcher_push_many(sdl_batcher *h, const uint8_t *arena, const uint64_t *
 int sdl_batcher_push_many_pairs(sdl_batcher *h, const uint8_t *arena, const uint64_t *offsets, size_t n_pairs,
                                 const uint32_t *labels, const uint64_t *label_offsets, size_t *n_emitted) {
     if (!h || !offsets || (!arena && n_pairs && offsets[2 * n_pairs])) return fail(SDL_ERR_ARG, "null argument");
-    if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push_many_pairs needs a handle created with pair = 1");
+    if (!h->pair_calls()) return fail(SDL_ERR_STATE, "sdl_batcher_push_many_pairs needs a handle created with pair = 1");
     return push_many_checked(h, arena, offsets, 2 * n_pairs, n_pairs, labels, label_offsets, n_emitted);
 }
 
@@ -1613,7 +1675,7 @@ int sdl_batcher_push_many_pairs(sdl_batcher *h, const uint8_t *arena, const uint
 int sdl_batcher_push_pair(sdl_batcher *h, const uint8_t *a, size_t len_a, const uint8_t *b, size_t len_b,
                           const uint32_t *labels, size_t n_labels, sdl_batch *out) {
     if (!h || (!a && len_a) || (!b && len_b) || (!labels && n_labels)) return fail(SDL_ERR_ARG, "null argument");
-    if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_batcher_push_pair needs a handle created with pair = 1");
+    if (!h->pair_calls()) return fail(SDL_ERR_STATE, "sdl_batcher_push_pair needs a handle created with pair = 1");
     if (h->cfg.pair == SDL_PAIR_MLM_NSP)
         return fail(SDL_ERR_UNSUPPORTED,
                     "sdl_batcher_push_pair under pair = 3: a call of one pair has nobody to draw a next sentence "
@@ -1631,6 +1693,14 @@ int sdl_batcher_push_pair(sdl_batcher *h, const uint8_t *a, size_t len_a, const 
         uint64_t loffs[2] = {0, (uint64_t)n_labels};
         const size_t before = h->outbox.size();
         h->process_host(both.empty() ? (const uint8_t *)"" : both.data(), offs, 2, labels, loffs);
+        if (h->pack()) {  // pair = 6: push_many_pairs of one pair, the front of the queue as in sdl_batcher_push
+            if (h->outbox.empty()) return 0;
+            HostBatch *bt = h->outbox.front();
+            h->outbox.pop_front();
+            if (out) fill_batch(h, bt, out);
+            else delete bt;
+            return 1;
+        }
         if (h->outbox.size() > before) {
             HostBatch *bt = h->outbox.back();
             h->outbox.pop_back();
@@ -1712,7 +1782,7 @@ int sdl_process_device_labels(sdl_batcher *h, const uint8_t *d_text, uint64_t te
                               uint64_t n_records, const uint32_t *d_labels, const uint64_t *d_label_offsets,
                               uint64_t first_record, void *stream, sdl_device_rows *out) {
     if (!h || !out || !d_offsets || (!d_text && text_len)) return fail(SDL_ERR_ARG, "null argument");
-    if (h->pair())
+    if (h->pair_calls())
         return fail(SDL_ERR_STATE, "sdl_process_device[_labels] on a handle created with pair = 1: use sdl_process_device_pairs");
     return process_device_checked(h, d_text, text_len, d_offsets, n_records, n_records, d_labels, d_label_offsets,
                                   first_record, stream, out);
@@ -1722,7 +1792,7 @@ int sdl_process_device_pairs(sdl_batcher *h, const uint8_t *d_text, uint64_t tex
                              uint64_t n_pairs, const uint32_t *d_labels, const uint64_t *d_label_offsets,
                              uint64_t first_record, void *stream, sdl_device_rows *out) {
     if (!h || !out || !d_offsets || (!d_text && text_len)) return fail(SDL_ERR_ARG, "null argument");
-    if (!h->pair()) return fail(SDL_ERR_STATE, "sdl_process_device_pairs needs a handle created with pair = 1");
+    if (!h->pair_calls()) return fail(SDL_ERR_STATE, "sdl_process_device_pairs needs a handle created with pair = 1");
     if (n_pairs >= (1ull << 31)) return fail(SDL_ERR_CAPACITY, "too many pairs in one call");
     return process_device_checked(h, d_text, text_len, d_offsets, 2 * n_pairs, n_pairs, d_labels, d_label_offsets,
                                   first_record, stream, out);
@@ -1750,6 +1820,9 @@ int sdl_batcher_set_fim(sdl_batcher *h, const sdl_fim *f) {
     if (!h->pack() || h->P.task != SDL_TASK_CLM)
         return fail(SDL_ERR_STATE, "sdl_batcher_set_fim needs a handle created with pack = 1 under the CLM task: "
                                    "fill-in-the-middle is defined for packed clm rows only");
+    if (h->pair_clm())
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_fim on a handle created with pair = 6: fill-in-the-middle over "
+                                   "prompt / completion examples is not built");
     if (h->in_multi)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_batcher_set_fim on a shard of an sdl_multi: the draw's record index is "
                                          "counted per handle; give each shard a handle of its own");
@@ -1782,6 +1855,9 @@ int sdl_batcher_set_best_fit(sdl_batcher *h, const sdl_best_fit *bf) {
     if (!h->pack() || h->P.task != SDL_TASK_CLM)
         return fail(SDL_ERR_STATE, "sdl_batcher_set_best_fit needs a handle created with pack = 1 under the CLM task: "
                                    "best-fit rows are defined for packed clm rows only");
+    if (h->pair_clm())
+        return fail(SDL_ERR_STATE, "sdl_batcher_set_best_fit on a handle created with pair = 6: best-fit rows over "
+                                   "prompt / completion examples are not built");
     if (h->in_multi)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_batcher_set_best_fit on a shard of an sdl_multi: the windows are cut "
                                          "from one handle's calls; give each shard a handle of its own");
@@ -1899,6 +1975,9 @@ int sdl_multi_create(const sdl_config *cfg, const char *tokenizer_path, const ch
     if (!cfg || !devices || !out || n_devices == 0) return fail(SDL_ERR_ARG, "null argument or no devices");
     if (cfg->pair == 1)
         return fail(SDL_ERR_UNSUPPORTED, "sdl_multi_create with pair = 1: sentence pairs are not sharded over several handles");
+    if (cfg->pair == SDL_PAIR_CLM_COMPLETION)
+        return fail(SDL_ERR_UNSUPPORTED,
+                    "sdl_multi_create with pair = 6: prompt / completion examples are not sharded over several handles");
     if (cfg->pair >= SDL_PAIR_MLM && cfg->pair <= SDL_PAIR_MLM_SOP)
         return fail(SDL_ERR_UNSUPPORTED,
                     "sdl_multi_create with pair = 2..4: sentence pairs are not sharded over several handles (a next-"

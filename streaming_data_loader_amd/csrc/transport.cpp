@@ -137,6 +137,8 @@ int sdl_json_to_frames(sdl_batcher *h, const uint8_t *jsonl, uint64_t len, uint6
     const int task = h->cfg.task;
     if (h->pair_mlm())
         return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: pair = 2..4 is not supported (one text member a line)");
+    if (h->pair_clm())
+        return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: pair = 6 is not supported (one text member a line)");
     if (h->pair())
         return fail(SDL_ERR_UNSUPPORTED, "sdl_json_to_frames: pair = 1 is not supported (one text member a line)");
     if (task != SDL_TASK_MLM && task != SDL_TASK_CLM && task != SDL_TASK_SPAN)

@@ -176,7 +176,7 @@ class DeviceBatcher:
         c.rng_mode = rng_mode
         c.mask_policy, c.mask_per_mille = mask_policy, mask_per_mille
         c.pack = int(pack)
-        c.pair = int(pair)  # native.SDL_PAIR_*: sentence pairs (process_pairs); True = 1, 2..4 under mlm
+        c.pair = int(pair)  # native.SDL_PAIR_*: sentence pairs (process_pairs); True = 1, 2..4 under mlm, 5 packed clm
         c.span_policy, c.span_noise_per_mille = span_policy, span_noise_per_mille
         c.avg_span_gap, c.avg_span_size = avg_span_gap, avg_span_size
         if min_ids is not None:
@@ -242,14 +242,17 @@ class DeviceBatcher:
         """Sentence pairs (pair=True; sdl_process_device_pairs): A_r is text range 2r and B_r range
         2r + 1 of the device arena (2 n_pairs + 1 offsets, arena_from_pairs); labels per pair
         (n_pairs + 1 label offsets; ignored under mlm).  One [CLS] A [SEP] B [SEP] row per pair;
-        under pair=2..4 (mlm) the result's pair_labels() holds each row's drawn label."""
+        under pair=2..4 (mlm) the result's pair_labels() holds each row's drawn label.  Under
+        pack=1, pair=native.SDL_PAIR_CLM_COMPLETION (clm) A_r is a prompt and B_r its completion:
+        packed rows with labels -100 on the prompt ids, position_ids() as for packed rows."""
         out = native.DeviceRows()
         native.check(native.load().sdl_process_device_pairs(
             self._h, ctypes.c_void_p(text_ptr), text_len, ctypes.c_void_p(offsets_ptr), n_pairs,
             ctypes.c_void_p(labels_ptr or None), ctypes.c_void_p(label_offsets_ptr or None), first_record,
             ctypes.c_void_p(stream or None), ctypes.byref(out)))
         return DeviceResult(self._h, out, n_pairs, self.cfg.sequence_length, self.cfg.batch_size, self.cfg.device,
-                            stream, pair_ptr=native.load().sdl_device_pair_labels(self._h))
+                            stream, native.load().sdl_device_position_ids(self._h),
+                            native.load().sdl_device_pair_labels(self._h))
 
     def json_text(self, jsonl_ptr, jsonl_len, stream=0):
         """The provider's JsonText filter on the device (sdl_json_text_device):

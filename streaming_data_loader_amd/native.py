@@ -25,6 +25,7 @@ SDL_SPAN_REFERENCE, SDL_SPAN_T5 = 0, 1
 # sdl_config.pair: one text per record, pair rows (single-class / multi-label), then mlm pair rows
 # with the pair label 0, a next-sentence draw, a sentence-order draw
 SDL_PAIR_NONE, SDL_PAIR_ROWS, SDL_PAIR_MLM, SDL_PAIR_MLM_NSP, SDL_PAIR_MLM_SOP = 0, 1, 2, 3, 4
+SDL_PAIR_CLM_COMPLETION = 6  # packed clm: prompt / completion examples with completion-only labels
 
 # every symbol include/sdl_batcher.h declares
 EXPORTS = [
